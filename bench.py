@@ -99,6 +99,25 @@ def keyframe_step(graph):
         graph.update(None, None, use_inactive=True)
 
 
+NET_SAMPLE = 1 << 20        # entries of the per-edge GRU state kept by --dump-outputs (the whole state is 184 MB in fp32)
+
+
+def dump_outputs(out_dir, video, graph):
+    """--dump-outputs: what the timed keyframe step leaves its caller, after the last timed step, as float32 .npy files
+    (~40 MB): the window's poses, 1/8 and full-resolution disparities and damping (DepthVideo), and the factors' BA
+    targets and weights (FactorGraph).  The fp16 GRU state enters as a fixed seeded sample of NET_SAMPLE entries."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    net = graph.net.reshape(-1)
+    pick = torch.randint(0, net.numel(), (NET_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+    n = NUM_KF
+    arrays = {"poses": video.poses[:n], "disps": video.disps[:n], "disps_up": video.disps_up[:n],
+              "damping": graph.damping[:n], "target": graph.target, "weight": graph.weight,
+              "net_sample": net[pick.to(net.device)]}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def global_ba_stress(device, num_kf=200, num_edges=1200, shape="Scan"):
     """BASELINE configs[3] stress shape: >= 200 keyframes, 1200 edges at 30x40 maps -- wall time of
     ONE full-BA `update_lowmem` step (alt-corr lookups in chunks of 13 source keyframes + update operator + a
@@ -1051,7 +1070,11 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed step's outputs after its last step to DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus, sys.argv[1:]))
@@ -1065,6 +1088,11 @@ def main():
     if os.environ.get("GS_BENCH_LAUNCH_ONLY") == "1":
         return launch_only(world, rank)
     assert torch.cuda.is_available(), "bench.py needs an MI355X (there is no CPU path)"
+    # stdout carries the result line alone: whatever else this process prints, from Python or through C stdio (RCCL's
+    # banner), goes to stderr until the line is printed
+    sys.stdout.flush()
+    line_fd = os.dup(1)
+    os.dup2(2, 1)
     # GS_BENCH_SMOKE_ONE_GPU=1: functional smoke test of the N>1 code path on a 1-GPU box (all ranks
     # on cuda:0, gloo instead of RCCL -- RCCL refuses two ranks on one device).  Never used for numbers.
     smoke_one_gpu = os.environ.get("GS_BENCH_SMOKE_ONE_GPU") == "1"
@@ -1114,6 +1142,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
     finite = bool(torch.isfinite(video.poses).all()) and bool(torch.isfinite(video.disps).all())
+    if args.dump_outputs and rank == 0:         # before the legs below, which run more updates on this graph
+        dump_outputs(args.dump_outputs, video, graph)
 
     ms_per_step = 1e3 * elapsed / args.steps
     value = world * args.steps / elapsed          # aggregate keyframes/s over all replicas
@@ -1258,8 +1288,9 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     flush_c_stdio()                             # every C-level byte of this process is out before the line is printed:
-    if rank == 0:                               # the line stays the LAST line of stdout
-        sys.stdout.flush()
+    sys.stdout.flush()                          # the line stays the ONLY line of stdout
+    os.dup2(line_fd, 1)
+    if rank == 0:
         print(json.dumps(line), flush=True)
 
 

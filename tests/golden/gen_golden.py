@@ -34,6 +34,7 @@ What the fixtures therefore PIN is every line of reference Python on the hot pat
                          compositing, compute_sdf_error                       -> neus_forward.npz, neus_forward_cases.npz
   * InstantNeuS.py       the SAME forward differentiated by its own autograd graph (autograd.grad(create_graph=True) +
                          backward) on a twice-differentiable stand-in: every trained parameter's gradient -> neus_backward.npz
+  * the classes slam.py constructs  constructor parameters of the classes the package mirrors  -> reference_signatures.json
   * lib/*.cu             the reference's CUDA kernels themselves, compiled for the CPU (oracle/build_ref.py): ba,
                          frame_distance, projmap, iproj, depth_filter on seeded inputs             -> reference_kernels.npz
   * modules/corr.py + lib/altcorr_kernel.cu  AltCorrBlock over the reference's own alt-corr kernel, 4 levels, 9 edges
@@ -1360,6 +1361,31 @@ def gen_lowmem():
     save("update_lowmem.npz", **arrays)
 
 
+SIGNATURE_CLASSES = {"depth_video": "DepthVideo", "factor_graph": "FactorGraph", "frontend": "Frontend", "backend": "Backend",
+                     "motion_filter": "MotionFilter", "multiview_filter": "MultiviewFilter",
+                     "trajectory_filler": "PoseTrajectoryFiller", "droid_net": "DroidNet", "InstantNeuS": "InstantNeuS"}
+
+
+def gen_signatures():
+    """the constructor parameters (name, kind, has a default) of the reference classes the package mirrors: what
+    slam.py may pass them (tests/test_slam_contract_cpu.py)"""
+    import inspect
+    import json
+    from go_slam_amd.dropin import _torch_scatter
+    sys.modules.setdefault("torch_scatter", _torch_scatter())
+    for name in ("open3d", "cv2", "pyrender", "matplotlib", "matplotlib.pyplot", "evo"):
+        sys.modules.setdefault(name, types.ModuleType(name))
+    sys.path.insert(0, REF)
+    out = {}
+    for mod, cls in SIGNATURE_CLASSES.items():
+        init = getattr(importlib.import_module(f"src.{mod}"), cls).__init__
+        out[f"src.{mod}"] = [[p.name, p.kind.name, p.default is not inspect.Parameter.empty]
+                             for p in inspect.signature(init).parameters.values() if p.name != "self"]
+    with open(os.path.join(HERE, "reference_signatures.json"), "w") as f:
+        json.dump(out, f, indent=1)
+    print("wrote reference_signatures.json", {k: len(v) for k, v in out.items()})
+
+
 if __name__ == "__main__":
     assert os.path.isdir(REF), "the reference tree is needed to (re)generate the fixtures"
     install_stubs()
@@ -1391,3 +1417,4 @@ if __name__ == "__main__":
     gen_reference_kernels()
     gen_reference_kernels_bench()
     gen_reference_altcorr_pyramid()
+    gen_signatures()
