@@ -213,7 +213,29 @@ __device__ __forceinline__ float gs_wave_sum(float v) {
 // measured 17 us of the 53 us global-context kernel and a tenth of the GRU convolutions' epilogues).  After the fp16
 // rounding the result differs from the exactly divided one for ~1 element in 10^4 (by one fp16 ulp).
 __device__ __forceinline__ float gs_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float gs_tanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
+// tanh: 1 - 2 / (1 + e^2x) cancels near zero (absolute error ~1e-7 whatever x is: several fp16 ulps of tanh(x) for |x| < 1e-4,
+// where x itself goes through with z = 1), so below |x| = 1/16 the odd Taylor polynomial to x^5 (truncation 0.054 x^7:
+// < 4e-9 relative there) is taken instead; both are computed and selected, no branch.  NaN and +-inf take the formula.
+__device__ __forceinline__ float gs_tanh(float x) {
+  const float x2 = x * x;
+  const float p = fmaf(x * x2, fmaf(x2, 2.0f / 15.0f, -1.0f / 3.0f), x);
+  const float e = 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x));
+  return fabsf(x) < 0.0625f ? p : e;
+}
+
+// (count, mean, M2) of a set of samples and Chan et al.'s merge of two such sets (fp32)
+struct GsMoments { float n, mean, m2; };
+__device__ __forceinline__ GsMoments gs_moments_merge(const GsMoments a, const GsMoments b) {
+  if (b.n == 0.0f) return a;
+  if (a.n == 0.0f) return b;
+  GsMoments r;
+  r.n = a.n + b.n;
+  const float d = b.mean - a.mean;
+  const float f = b.n / r.n;
+  r.mean = a.mean + d * f;
+  r.m2 = a.m2 + b.m2 + d * d * a.n * f;
+  return r;
+}
 
 // Sums of N per-lane values over the wave, "reduce-scatter" form: instead of N full butterflies (gs_wave_sum: 11
 // instructions per value) the value array is halved at every lane-bit step -- a lane keeps the even or the odd element of

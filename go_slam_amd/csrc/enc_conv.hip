@@ -27,7 +27,7 @@ typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 typedef float float16v __attribute__((ext_vector_type(16)));
 
 struct EncArgs {
-  float* stats;                       // [n][workgroups per image][cout][2] sums of (v - bias) and (v - bias)^2, or nullptr
+  float* stats;                       // [n][workgroups per image][cout] (count, mean, M2) of v, or nullptr
   const _Float16* stat_bias;          // [cout] fp16: v = half(half(conv) + bias), the tensor torch normalises
   int cout;
   const _Float16* x; int xs;          // input NHWC, `xs` halves per pixel
@@ -58,21 +58,25 @@ __device__ __forceinline__ void store_tile(const float16v& acc, _Float16* tile, 
   const int r = lane & 31, kh = lane >> 5;
   if (A.stats) {
     // InstanceNorm statistics in the convolution's epilogue (one launch less per normalisation, and the statistics pass
-    // over the tensor is gone): per channel the sums of d and d^2 over this wave's pixels, d = v - bias with v =
-    // half(half(conv) + bias) the fp16 value torch normalises -- shifting by the bias keeps d centred on the
-    // convolution's own (small) mean, so plain fp32 sums stay well conditioned and the workgroups' partial sums merge
-    // by ADDITION (instnorm_final_sums_kernel; Chan merges cost a division per chunk and channel).
+    // over the tensor is gone): per channel the count, mean and M2 of this wave's pixels of v = half(half(conv) + bias),
+    // the fp16 value torch normalises.  The sums are shifted by the wave's first pixel k (per channel), d = v - k, so
+    // that they stay well conditioned whatever the channel's mean (the bias does not centre v: the convolution's own
+    // mean, Sum w E[x], is not small after a ReLU); the workgroup merges its waves' moments and publishes one
+    // (count, mean, M2) per channel, and instnorm_final_sums_kernel merges those.
     const int nvalid = min(32, A.wo - ox0);
-    float sv[32];                                  // [0..15] = d, [16..31] = d^2 of this lane's pixel, per accumulator register
+    float v[16], sv[32];                           // sv: [0..15] = d, [16..31] = d^2 of this lane's pixel, per accumulator register
 #pragma unroll
     for (int e16 = 0; e16 < 16; ++e16) {
-      const float v = (float)(_Float16)acc[e16];
-      float d = v;
-      if (A.stat_bias) {
-        const float bsh = (float)sbias.q[e16 >> 2][e16 & 3];
-        d = (float)(_Float16)(v + bsh) - bsh;
-      }
-      if (r >= nvalid) d = 0.0f;
+      v[e16] = (float)(_Float16)acc[e16];
+      if (A.stat_bias) v[e16] = (float)(_Float16)(v[e16] + (float)sbias.q[e16 >> 2][e16 & 3]);
+    }
+    float k[16];                                   // the shift of channel (e16, kh): pixel 0 of the tile, lane 0 / lane 32
+#pragma unroll
+    for (int e16 = 0; e16 < 16; ++e16) {
+      const float k0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v[e16]), 0));
+      const float k1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v[e16]), 32));
+      k[e16] = kh ? k1 : k0;
+      const float d = r < nvalid ? v[e16] - k[e16] : 0.0f;
       sv[e16] = d;
       sv[16 + e16] = d * d;
     }
@@ -87,7 +91,16 @@ __device__ __forceinline__ void store_tile(const float16v& acc, _Float16* tile, 
       const int idx = (int)(__brev((unsigned)(lane & 31)) >> 27);
       const int e16 = idx & 15;
       const int ch = c0 + 8 * (e16 >> 2) + 4 * kh + (e16 & 3);
-      red[2 * ch + (idx >> 4)] = sv[0];       // this wave's own slab: 64 lanes, 64 distinct (channel, moment) slots
+      const float other = __shfl_xor(sv[0], 1, 64);      // bit 4 of idx is bit 0 of the lane: the pair's other sum
+      float kk = 0.0f;
+#pragma unroll
+      for (int j = 0; j < 16; ++j) kk = j == e16 ? k[j] : kk;
+      if (!(lane & 1)) {                                  // idx < 16: sv[0] = S1, other = S2 of channel ch
+        const float n = (float)nvalid, m = sv[0] / n;
+        red[3 * ch + 0] = n;                              // this wave's own slab
+        red[3 * ch + 1] = kk + m;
+        red[3 * ch + 2] = fmaxf(other - sv[0] * m, 0.0f);
+      }
     }
   }
 #pragma unroll
@@ -117,32 +130,49 @@ __device__ __forceinline__ void store_tile(const float16v& acc, _Float16* tile, 
 
 // KS x KS convolution (KS in {1, 3}), padding KS / 2, stride STRIDE, CIN input channels; `mtiles` = c_out / 32
 // workgroup-level tail of the statistics: zero / publish the per-channel LDS accumulators
-// (one slab of 2 * cout sums per wave, written with plain stores and added in wave order: the statistics -- and with
+// (one slab of 3 * cout values per wave, (count, mean, M2) per channel, merged in wave order: the statistics -- and with
 // them the encoder features -- are bitwise reproducible; floating-point LDS atomics from four waves were not)
-__device__ __forceinline__ void red_init(float* red, int n2, int slab) {
+__device__ __forceinline__ void red_init(float* red, int n3, int slab) {
   for (int w = 0; w < 4; ++w)
-    for (int i = threadIdx.x; i < n2; i += 256) red[w * slab + i] = 0.0f;
+    for (int i = threadIdx.x; i < n3; i += 256) red[w * slab + i] = 0.0f;
   __syncthreads();
 }
 __device__ __forceinline__ void red_publish(const float* red, const EncArgs& A, int img, int slab) {
   __syncthreads();
-  float* dst = A.stats + ((size_t)img * gridDim.x + blockIdx.x) * A.cout * 2;
-  for (int i = threadIdx.x; i < 2 * A.cout; i += 256)
-    dst[i] = ((red[i] + red[slab + i]) + red[2 * slab + i]) + red[3 * slab + i];
+  GsMoments* dst = reinterpret_cast<GsMoments*>(A.stats) + ((size_t)img * gridDim.x + blockIdx.x) * A.cout;
+  for (int c = threadIdx.x; c < A.cout; c += 256) {
+    // the four waves' moments merged with ONE division (the waves that do not cover channel c hold n = 0): shifted by
+    // the first covering wave's mean mr, N = Sum n, S = Sum n (m - mr), mean = mr + S / N, M2 = Sum (M2 + n (m - mr)^2)
+    // - S^2 / N (sequential Chan merges were four dependent divisions at the tail of every workgroup)
+    float n[4], m[4], q[4];
+#pragma unroll
+    for (int w = 0; w < 4; ++w) { n[w] = red[w * slab + 3 * c]; m[w] = red[w * slab + 3 * c + 1]; q[w] = red[w * slab + 3 * c + 2]; }
+    const float mr = n[0] > 0.0f ? m[0] : n[1] > 0.0f ? m[1] : n[2] > 0.0f ? m[2] : m[3];
+    float N = 0.0f, S = 0.0f, Q = 0.0f;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const float dm = m[w] - mr;
+      N += n[w];
+      S += n[w] * dm;
+      Q += q[w] + n[w] * dm * dm;
+    }
+    const float ds = N > 0.0f ? S / N : 0.0f;
+    dst[c] = GsMoments{N, mr + ds, fmaxf(Q - S * ds, 0.0f)};
+  }
 }
 
 template <int KS, int CIN, int STRIDE>
 __global__ __launch_bounds__(256) void enc_conv_kernel(EncArgs A, int mtiles) {
   constexpr int KSTEPS = CIN / 16, PAD = KS / 2;
   __shared__ __attribute__((aligned(16))) _Float16 tiles[4][32 * 40];
-  constexpr int SLAB = 2 * 256;
+  constexpr int SLAB = 3 * 256;
   __shared__ float red[4 * SLAB];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int groups_x = (A.wo + 31) / 32;
   const int img = blockIdx.y;                     // a workgroup never straddles two images (its statistics are per image)
   const int wave_id = blockIdx.x * 4 + wv;
   const bool active = wave_id < A.ho * groups_x * mtiles;
-  if (A.stats) red_init(red, 2 * A.cout, SLAB);
+  if (A.stats) red_init(red, 3 * A.cout, SLAB);
   const int mt = wave_id % mtiles;
   const int pg = wave_id / mtiles;
   const int gx = pg % groups_x;
@@ -183,14 +213,14 @@ __global__ __launch_bounds__(256) void enc_conv_kernel(EncArgs A, int mtiles) {
 // the stem: 7 x 7, stride 2, padding 3, 4 (RGB0) -> 32 channels.  K = 7 kernel rows x 32 (8 taps x 4 channels, tap 7 = 0)
 __global__ __launch_bounds__(256) void enc_stem_kernel(EncArgs A) {
   __shared__ __attribute__((aligned(16))) _Float16 tiles[4][32 * 40];
-  constexpr int SLAB = 2 * 32;
+  constexpr int SLAB = 3 * 32;
   __shared__ float red[4 * SLAB];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int groups_x = (A.wo + 31) / 32;
   const int img = blockIdx.y;
   const int wave_id = blockIdx.x * 4 + wv;
   const bool active = wave_id < A.ho * groups_x;
-  if (A.stats) red_init(red, 2 * 32, SLAB);
+  if (A.stats) red_init(red, 3 * 32, SLAB);
   const int gx = wave_id % groups_x;
   const int oy = active ? wave_id / groups_x : 0;
   const int r = lane & 31, kh = lane >> 5;
@@ -254,7 +284,7 @@ extern "C" size_t gs_enc_conv_wpack_elems(int ksize, int c_in, int c_out) {
   return (size_t)ksize * ksize * c_in * c_out;
 }
 
-// workgroups per image = partial-sum slabs per image the epilogue statistics produce
+// workgroups per image = moment slabs per image the epilogue statistics produce
 extern "C" int gs_enc_conv_stat_chunks(int h_out, int w_out, int c_out) {
   return (h_out * ((w_out + 31) / 32) * (c_out / 32) + 3) / 4;
 }

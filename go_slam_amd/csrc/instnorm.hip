@@ -25,19 +25,8 @@ typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
 constexpr int IN_CHUNK = 256;      // pixels per statistics workgroup
 
-struct Moments { float n, mean, m2; };
-
-__device__ __forceinline__ Moments merge(const Moments a, const Moments b) {   // Chan et al.
-  if (b.n == 0.0f) return a;
-  if (a.n == 0.0f) return b;
-  Moments r;
-  r.n = a.n + b.n;
-  const float d = b.mean - a.mean;
-  const float f = b.n / r.n;
-  r.mean = a.mean + d * f;
-  r.m2 = a.m2 + b.m2 + d * d * a.n * f;
-  return r;
-}
+typedef GsMoments Moments;
+__device__ __forceinline__ Moments merge(const Moments a, const Moments b) { return gs_moments_merge(a, b); }   // Chan et al.
 
 // partial: [n][nblk][c] Moments
 __global__ __launch_bounds__(256) void instnorm_stats_kernel(const _Float16* __restrict__ x,
@@ -147,44 +136,62 @@ __global__ __launch_bounds__(256) void instnorm_final_kernel(const Moments* __re
   }
 }
 
-// The same for partial SUMS [n][nblk][c][2] of d = v - shift and d^2 (gs_enc_conv's epilogue statistics, shift = the
-// convolution's bias): plain additions, eight loads in flight per thread, then mean = shift + S1 / N and the biased
-// variance (S2 - S1^2 / N) / N.
-constexpr int FS_NT = 1024;      // one workgroup per image merges <= 600 partial sums per channel: with 256 threads that was
+// The same for the moments gs_enc_conv's epilogue leaves, one (count, mean, M2) per workgroup and channel [n][nblk][c]
+// (every wave shifts its sums by its own first pixel, the workgroup merges its waves by Chan).  No division per slab:
+// per channel, in fp64, the sums of n (mean - K) and M2 + n (mean - K)^2 with K = the first slab's mean, eight loads in
+// flight per thread.  (The slabs used to hold fp32 sums of d = v - bias and d^2, merged by fp32 addition: d is not
+// centred -- its mean is the convolution's own, Sum w E[x], large after a ReLU -- and at mean / spread 10^2 the fp32
+// sums lost 0.2% of invstd on a 240 x 320 map.)
+constexpr int FS_NT = 1024;      // one workgroup per image merges <= 600 slabs per channel: with 256 threads that was
                                  // 9-10 dependent round trips of 64 chunks (6.5 us, 15 times per input frame); 1024 threads
                                  // take 256 chunks per round trip.  The order of the additions is fixed (thread `part` adds
-                                 // its chunks in ascending order, thread 0..c-1 then adds the parts in ascending order).
-__global__ __launch_bounds__(FS_NT) void instnorm_final_sums_kernel(const float* __restrict__ sums, int nblk, int c, int hw,
-                                                                    const _Float16* __restrict__ shift, float eps,
-                                                                    float* __restrict__ final_) {
-  __shared__ float sm[FS_NT][2];
+                                 // its chunks in ascending order, then the parts are added as a binary tree).
+__global__ __launch_bounds__(FS_NT) void instnorm_final_sums_kernel(const Moments* __restrict__ partial, int nblk, int c,
+                                                                    float eps, float* __restrict__ final_) {
+  __shared__ double sm[FS_NT][3];
   const int img = blockIdx.x, tid = threadIdx.x;
   const int per = FS_NT / c;                                  // threads per channel (c in {32, 64, 128, 256})
   const int ch = tid % c, part = tid / c;
-  float a1 = 0.0f, a2 = 0.0f;
-  const float2* src = reinterpret_cast<const float2*>(sums) + (size_t)img * nblk * c + ch;
+  const Moments* src = partial + (size_t)img * nblk * c + ch;
+  // the shift: slab 0's mean (with 256 channels workgroup 0 covers channels 0..127 only: slab 1 then)
+  const Moments k0 = src[0], k1 = src[(size_t)min(1, nblk - 1) * c];
+  const double K = (double)(k0.n > 0.0f ? k0.mean : k1.mean);
+  double sn = 0.0, s1 = 0.0, s2 = 0.0;
   for (int b = part; b < nblk; b += 8 * per) {
-    float2 v[8];
+    Moments v[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const int bb = b + u * per;
       v[u] = src[(size_t)min(bb, nblk - 1) * c];
-      if (bb >= nblk) v[u] = make_float2(0.0f, 0.0f);
+      if (bb >= nblk) v[u] = Moments{0.0f, 0.0f, 0.0f};
     }
 #pragma unroll
-    for (int u = 0; u < 8; ++u) { a1 += v[u].x; a2 += v[u].y; }
+    for (int u = 0; u < 8; ++u) {
+      const double nn = (double)v[u].n, dm = (double)v[u].mean - K;
+      sn += nn;
+      s1 += nn * dm;
+      s2 += (double)v[u].m2 + nn * dm * dm;
+    }
   }
-  sm[tid][0] = a1;
-  sm[tid][1] = a2;
+  sm[tid][0] = sn;
+  sm[tid][1] = s1;
+  sm[tid][2] = s2;
   __syncthreads();
+  for (int half = per / 2; half >= 1; half /= 2) {          // the parts added as a tree (per is a power of two)
+    if (part < half) {
+      sn += sm[tid + half * c][0];
+      s1 += sm[tid + half * c][1];
+      s2 += sm[tid + half * c][2];
+      sm[tid][0] = sn;
+      sm[tid][1] = s1;
+      sm[tid][2] = s2;
+    }
+    __syncthreads();
+  }
   if (tid < c) {
-    for (int q = 1; q < per; ++q) { a1 += sm[q * c + tid][0]; a2 += sm[q * c + tid][1]; }
-    // E[d^2] - E[d]^2 in fp64: on a near-constant map the two terms agree to ~7 digits and their fp32 difference would be
-    // of the order of eps itself (the sums are of d = v - bias, already centred on the convolution's own mean)
-    const double n = (double)hw;
-    const double mean_d = (double)a1 / n;
-    const double var = fmax((double)a2 / n - mean_d * mean_d, 0.0);
-    final_[((size_t)img * c + tid) * 2 + 0] = (shift ? (float)shift[tid] : 0.0f) + (float)mean_d;
+    const double mean_d = sn > 0.0 ? s1 / sn : 0.0;
+    const double var = sn > 0.0 ? fmax(s2 / sn - mean_d * mean_d, 0.0) : 0.0;
+    final_[((size_t)img * c + tid) * 2 + 0] = (float)(K + mean_d);
     final_[((size_t)img * c + tid) * 2 + 1] = (float)(1.0 / sqrt(var + (double)eps));
   }
 }
@@ -281,7 +288,7 @@ extern "C" int gs_norm_act(const void* x, const void* bias, const void* skip, vo
       GS_CHECK_LAUNCH("instnorm_stats");
     }
     if (stat_chunks > 0)
-      instnorm_final_sums_kernel<<<n, FS_NT, 0, st>>>((const float*)partial, nblk, channels, hw, (const _Float16*)bias, eps, final_);
+      instnorm_final_sums_kernel<<<n, FS_NT, 0, st>>>(partial, nblk, channels, eps, final_);
     else
       instnorm_final_kernel<<<n, 256, 0, st>>>(partial, nblk, channels, eps, final_);
     GS_CHECK_LAUNCH("instnorm_final");

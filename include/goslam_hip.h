@@ -306,7 +306,7 @@ int gs_segment_mean(const void* x, int x_stride, const float* in_bias, int in_re
  *   y = relu_out ? max(t, 0) : t
  * workspace: gs_norm_act_workspace_bytes bytes (not needed when instance_norm == 0).  stat_chunks > 0: the statistics pass
  * is skipped -- gs_enc_conv, given the same workspace as `stats_ws`, already wrote stat_chunks = gs_enc_conv_stat_chunks
- * (h_out, w_out, c_out) partial-sum slabs per image in its epilogue (workspace: gs_norm_act_workspace_bytes_chunks). */
+ * (h_out, w_out, c_out) moment slabs per image in its epilogue (workspace: gs_norm_act_workspace_bytes_chunks).    */
 size_t gs_norm_act_workspace_bytes(int n, int hw, int channels);
 size_t gs_norm_act_workspace_bytes_chunks(int n, int chunks, int channels);
 /* The frame encoders' convolutions (src/modules/extractor.py:61-126: BasicEncoder.conv1 7x7 / stride 2, the residual
@@ -319,7 +319,8 @@ size_t gs_norm_act_workspace_bytes_chunks(int n, int chunks, int channels);
  * [t][s][m][l][e] = W[32 m + (l & 31)][16 s + 8 (l >> 5) + e][t / ksize][t % ksize]; the stem: [7][2][64][8] with
  * [dy][s][l][e] = W[l & 31][e % 4][dy][4 s + 2 (l >> 5) + e / 4] (0 for channel 3 and tap 7).
  * stats_ws (optional): the gs_norm_act workspace of the InstanceNorm that follows -- the epilogue leaves per workgroup
- * and channel the sums of d and d^2, d = half(conv + stat_bias) - stat_bias (stat_bias f16 [c_out], optional), there, and
+ * and channel the count, mean and M2 (sums shifted by each wave's first pixel) of v = half(half(conv) + stat_bias)
+ * (stat_bias f16 [c_out], optional) there, and
  * gs_norm_act is then called with the SAME bias and stat_chunks = gs_enc_conv_stat_chunks(h_out, w_out, c_out).     */
 size_t gs_enc_conv_wpack_elems(int ksize, int c_in, int c_out);
 int gs_enc_conv_stat_chunks(int h_out, int w_out, int c_out);
