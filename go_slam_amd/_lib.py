@@ -107,6 +107,12 @@ SIGNATURES = {
                                        + [c_int, c_float, c_int, _P, c_int, c_int, _P, c_size_t, _P, _P, _P]),
     "gs_neus_bin_workspace_bytes": (c_size_t, [c_int]),
     "gs_ray_draw": (c_int, [_P] * 7 + [c_int] * 4 + [c_float] * 4 + [_P] * 5),
+    "gs_sdf_lattice": (c_int, [_P] * 3 + [c_int] * 3 + [_P] * 6 + [_P]),
+    "gs_mcubes_workspace_bytes": (c_size_t, [c_int] * 3),
+    "gs_mcubes_count": (c_int, [_P, c_int, c_int, c_int, c_float, _P, c_size_t, _P]),
+    "gs_mcubes_scan": (c_int, [c_int, c_int, c_int, _P, c_size_t, _P, _P]),
+    "gs_mcubes_emit": (c_int, [_P, c_int, c_int, c_int, c_float, _P, c_size_t, ctypes.c_longlong, ctypes.c_longlong,
+                               _P, _P, _P]),
 }
 
 

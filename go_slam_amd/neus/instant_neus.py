@@ -201,6 +201,69 @@ class InstantNeuS(nn.Module):
         rgb = torch.cat(rgbs, dim=0).cpu().numpy()
         return (np.clip(rgb, 0, 1) * 255).astype(np.uint8)
 
+    @torch.no_grad()
+    def sdf_lattice(self, bound_min, bound_max, resolution):
+        """The volume `extract_fields` returns -- -sdf on a resolution^3 lattice over [bound_min, bound_max], -100
+        outside the realtime bound -- as a float32 device tensor, from one fused launch (gs_sdf_lattice): the point's
+        35-term dot product straight from the grid gathers, no feature written to memory, no gathers outside the
+        realtime bound.  The coordinates are built as extract_fields builds them, so both see the same points."""
+        dev = self.bound.device
+        lin = [torch.linspace(float(bound_min[k]), float(bound_max[k]), resolution, device=dev) for k in range(3)]
+        bound = torch.stack([bound_min.to(dev).float(), bound_max.to(dev).float()], dim=1).contiguous()
+        rt = self.realtime_bound.detach().float().contiguous()
+        net = self.sdf_network
+        w = net.sdf_layer.weight.detach().float().contiguous()      # row 0 = the first 35 floats
+        b = net.sdf_layer.bias.detach().float().contiguous()
+        u = torch.empty(resolution, resolution, resolution, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            rc = _lib.lib().gs_sdf_lattice(_lib.ptr(lin[0]), _lib.ptr(lin[1]), _lib.ptr(lin[2]), resolution, resolution,
+                                           resolution, _lib.ptr(bound), _lib.ptr(rt),
+                                           _lib.ptr(net.encoding.encoding.params_half()), _lib.ptr(w), _lib.ptr(b),
+                                           _lib.ptr(u), _lib.stream_ptr(dev))
+        _lib.check(rc, "InstantNeuS.sdf_lattice")
+        return u
+
+    @torch.no_grad()
+    def extract_geometry(self, resolution, threshold, c2w_ref=None, save_path='./mesh.ply', color=False):
+        """src/InstantNeuS.py:457-497 step for step: the lattice over `self.bound` (sdf_lattice), marching cubes at
+        `threshold` (neus.mesh.marching_cubes, on the GPU), vertices to world coordinates in float64, the optional
+        c2w_ref [4,4], faces kept only if all three vertices lie within realtime_bound +- 0.01, unreferenced vertices
+        dropped (order kept), vertex colours from `extract_color` when `color` (computed for the kept vertices only),
+        `export(save_path)` unless save_path is None.
+        Returns a neus.mesh.Mesh.  One deliberate difference: trimesh.Trimesh(...)'s default processing merges
+        vertices that coincide exactly (a lattice corner exactly at the level is reached from several edges) and drops
+        non-finite ones; this mesh keeps one vertex per crossing edge."""
+        import numpy as np
+        from .mesh import Mesh, marching_cubes
+        bound_min, bound_max = self.bound[:, 0], self.bound[:, 1]
+        u = self.sdf_lattice(bound_min, bound_max, resolution)
+        verts, faces = marching_cubes(u, threshold)
+        del u
+        b_max_np = bound_max.detach().cpu().numpy()
+        b_min_np = bound_min.detach().cpu().numpy()
+        vertices = verts.cpu().numpy().astype(np.float64)
+        faces = faces.cpu().numpy().astype(np.int64)
+        vertices = vertices / (resolution - 1.0) * (b_max_np - b_min_np)[None, :] + b_min_np[None, :]
+        if c2w_ref is not None:
+            c2w = (c2w_ref.detach().cpu().numpy() if isinstance(c2w_ref, torch.Tensor) else np.asarray(c2w_ref))
+            vertices_homo = np.concatenate([vertices, np.ones_like(vertices[:, :1])], axis=1)
+            vertices = np.matmul(c2w.astype(np.float64)[None, :, :], vertices_homo[:, :, None])[:, :3, 0]
+        eps = 0.01
+        rt = self.realtime_bound.detach().cpu().numpy()
+        bound_mask = np.all(vertices >= (rt[:, 0] - eps), axis=1) & np.all(vertices <= (rt[:, 1] + eps), axis=1)
+        faces = faces[bound_mask[faces].all(axis=1)]
+        # remove unreferenced vertices, keeping their relative order (trimesh's remove_unreferenced_vertices)
+        used = np.zeros(len(vertices), dtype=bool)
+        used[faces.reshape(-1)] = True
+        remap = np.cumsum(used) - 1
+        vertices, faces = vertices[used], remap[faces].reshape(-1, 3)
+        # colours of the kept vertices only: per vertex the reference's values, without colouring what is culled
+        vertex_colors = self.extract_color(bound=self.bound.clone(), vertices=vertices) if color else None
+        mesh = Mesh(vertices, faces, vertex_colors)
+        if save_path is not None:
+            mesh.export(save_path)
+        return mesh
+
     def _bounds_host(self):
         """(bound, realtime_bound) as two 6-float host arrays; cached so the hot path has no D2H."""
         if self._host_bounds is None:

@@ -265,6 +265,48 @@ int gs_map_step_post(const float* gram_chunks, int nchunk, float inv_loss_scale,
                      const float* loss_rays, const float* gerr, int n, float w_eikonal, int samples, const float* counts,
                      float* g32, gs_stream_t stream);
 
+/* Mesh extraction (InstantNeuS.extract_geometry, src/InstantNeuS.py:457-497; mesh.hip).
+ *
+ * gs_sdf_lattice: u f32 [nx,ny,nz] (z fastest) = -sdf(xs[i], ys[j], zs[k]) -- the volume InstantNeuS.extract_fields
+ *   returns -- in one launch: xs/ys/zs f32 [nx]/[ny]/[nz] (torch.linspace on the device, as extract_fields builds them);
+ *   bound, realtime_bound f32 [3,2]; grid f16 [total*2]; sdf_w0 f32 [35] = row 0 of sdf_layer.weight, sdf_b0 f32 [1] =
+ *   its bias[0].  A point not strictly inside realtime_bound gets -100 and gathers nothing.  Otherwise p = clamp((x - b0)
+ *   / span * 2 - 1, -1, 1) and the 16 levels at (p + 1) / 2 op by op as SDFNetwork._query / gs_grid_encode (the fp16
+ *   features equal gs_grid_encode's bit for bit), dotted with sdf_w0 in fp32 (fmaf, p first, then the levels in order),
+ *   plus sdf_b0.  1 <= nx, ny, nz <= 1024.
+ *
+ * Marching cubes over a float32 volume u [nx,ny,nz] (1 <= nx, ny, nz <= 1024), the mcubes.marching_cubes(u, level)
+ * contract: vertices in index space, x along axis 0.
+ *   - corner below iff u < level (NaN is not below); a lattice edge crosses iff exactly one endpoint is below; every
+ *     crossing edge gets exactly one vertex, shared by every cube touching it (also on a volume thinner than 2 along an
+ *     axis, where no cube exists and no face references it);
+ *   - vertex on the edge from its lower endpoint a0 (value u0) to a1 = a0 + 1: t = (level - u0) / (u1 - u0),
+ *     pos = a0 + t * (a1 - a0) in fp32 without contraction; the other two coordinates are the lattice coordinates;
+ *   - vertices in ascending linear index of the edge's lower endpoint, then axis x < y < z; faces in ascending linear
+ *     index of the cube's lowest corner, then the order of the case's table entry;
+ *   - the 256-case table resolves every cube face from its four corner classes alone (below corners meeting only
+ *     diagonally stay separated), so cubes sharing a face agree and the mesh has no cracks; triangles are wound so that
+ *     (v1 - v0) x (v2 - v0) points toward decreasing u.
+ * Three steps, no workgroup ever waits on another:
+ *   gs_mcubes_count: per point its crossing edges and in-workgroup vertex offset, per workgroup its V and F totals;
+ *   gs_mcubes_scan:  the workgroup totals' prefix (two launches; in place, so once per count) and totals = [V, F]
+ *                    (device int64 [2]) -- the one value the host reads, to size the outputs;
+ *   gs_mcubes_emit:  vertices f32 [n_vertices,3] and faces int32 [n_faces,3] (n_* = the totals).  Returns
+ *                    GS_ERR_UNSUPPORTED and launches nothing if either exceeds INT32_MAX; every store is bounded by
+ *                    n_vertices / n_faces; nothing is launched when both are 0.
+ * gs_mcubes_workspace_bytes: the three steps' transient device memory, 2 bytes per lattice point plus 8 per 256 points
+ *   (+ alignment): 272,642,048 B at 512^3, 2,181,136,384 B at 1024^3; 0 for unsupported sizes.            */
+int gs_sdf_lattice(const float* xs, const float* ys, const float* zs, int nx, int ny, int nz, const float* bound,
+                   const float* realtime_bound, const void* grid, const float* sdf_w0, const float* sdf_b0, float* u,
+                   gs_stream_t stream);
+size_t gs_mcubes_workspace_bytes(int nx, int ny, int nz);
+int gs_mcubes_count(const float* u, int nx, int ny, int nz, float level, void* workspace, size_t workspace_bytes,
+                    gs_stream_t stream);
+int gs_mcubes_scan(int nx, int ny, int nz, void* workspace, size_t workspace_bytes, long long* totals,
+                   gs_stream_t stream);
+int gs_mcubes_emit(const float* u, int nx, int ny, int nz, float level, const void* workspace, size_t workspace_bytes,
+                   long long n_vertices, long long n_faces, float* vertices, int* faces, gs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
