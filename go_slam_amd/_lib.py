@@ -113,6 +113,16 @@ SIGNATURES = {
     "gs_mcubes_scan": (c_int, [c_int, c_int, c_int, _P, c_size_t, _P, _P]),
     "gs_mcubes_emit": (c_int, [_P, c_int, c_int, c_int, c_float, _P, c_size_t, ctypes.c_longlong, ctypes.c_longlong,
                                _P, _P, _P]),
+    "gs_mesh_depth_workspace_bytes": (c_size_t, []),
+    "gs_mesh_depth": (c_int, [_P, c_int, _P, c_int, _P, c_int] + [c_float] * 4 + [c_int, c_int, c_float, c_float, _P, _P,
+                                                                                   c_size_t, _P]),
+    "gs_mesh_visibility": (c_int, [_P, c_int, _P, _P, c_int] + [c_float] * 4 + [c_int, c_int, c_float, _P, _P, _P]),
+    "gs_face_components_workspace_bytes": (c_size_t, [c_int]),
+    "gs_face_components": (c_int, [_P, c_int, _P, _P, c_size_t, _P]),
+    "gs_face_component_areas": (c_int, [_P, _P, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "gs_hull_extremes_workspace_bytes": (c_size_t, [c_int]),
+    "gs_hull_extremes": (c_int, [_P, c_int, _P, _P, c_size_t, _P]),
+    "gs_hull_prefilter": (c_int, [_P, c_int, _P, c_int, ctypes.c_double, _P, _P]),
 }
 
 

@@ -59,6 +59,31 @@ class Mesh:
             np.ascontiguousarray(vertex_colors, dtype=np.uint8).reshape(-1, 3)
         assert self.vertex_colors is None or len(self.vertex_colors) == len(self.vertices)
 
+    def update_faces(self, mask):
+        """trimesh's update_faces: keep the faces selected by a boolean mask or an index array, in order."""
+        mask = mask.detach().cpu().numpy() if isinstance(mask, torch.Tensor) else np.asarray(mask)
+        self.faces = np.ascontiguousarray(self.faces[mask]).reshape(-1, 3)
+
+    def remove_unreferenced_vertices(self):
+        """trimesh's remove_unreferenced_vertices: drop vertices no face uses, keeping the others' relative order."""
+        used = np.zeros(len(self.vertices), dtype=bool)
+        used[self.faces.reshape(-1)] = True
+        remap = np.cumsum(used) - 1
+        self.vertices = np.ascontiguousarray(self.vertices[used])
+        self.faces = np.ascontiguousarray(remap[self.faces]).reshape(-1, 3)
+        if self.vertex_colors is not None:
+            self.vertex_colors = np.ascontiguousarray(self.vertex_colors[used])
+
+    @property
+    def area(self):
+        """Total surface area: the sum of 0.5 |(v1 - v0) x (v2 - v0)| over the faces, in float64."""
+        v = self.vertices[self.faces]
+        return float(0.5 * np.linalg.norm(np.cross(v[:, 1] - v[:, 0], v[:, 2] - v[:, 0]), axis=1).sum())
+
+    def copy(self):
+        return Mesh(self.vertices.copy(), self.faces.copy(),
+                    None if self.vertex_colors is None else self.vertex_colors.copy())
+
     def export(self, path):
         """Binary little-endian PLY: double x, y, z (+ uchar red, green, blue when coloured), faces as uchar-counted int
         lists.  Returns `path`."""

@@ -307,6 +307,82 @@ int gs_mcubes_scan(int nx, int ny, int nz, void* workspace, size_t workspace_byt
 int gs_mcubes_emit(const float* u, int nx, int ny, int nz, float level, const void* workspace, size_t workspace_bytes,
                    long long n_vertices, long long n_faces, float* vertices, int* faces, gs_stream_t stream);
 
+/* ---- mesh culling (Mesher.cull_mesh, src/mesher.py:155-240), csrc/cull.hip ----
+ *
+ * gs_mesh_depth: depth maps f32 [n_poses,H,W] of a mesh (vertices f32 [V,3], faces i32 [F,3]) at n_poses world-to-camera
+ * matrices w2c f32 [n_poses,3,4] (OpenCV convention; the host inverts c2w in float64).  Replaces extract_depth_from_mesh
+ * (src/mesher.py:444-480: pyrender IntrinsicsCamera, DEPTH_ONLY | SKIP_CULL_FACES, znear 0.001, zfar = far).
+ *   - pixel (row r, column c) holds the camera-space z of the nearest surface along the ray through the pixel centre
+ *     (u, v) = (c + 0.5, r + 0.5): the GL pixel centre after pyrender's vertical flip.  (Mesher.point_masks samples the
+ *     same maps at (u, v) = (c, r) through grid_sample(align_corners=True); that half-pixel mismatch is the reference's.)
+ *   - 0 where no face covers the pixel centre, or where every hit is beyond zfar;
+ *   - no back-face culling; the part of a triangle with z >= znear renders (camera-space near clipping, exact: the ray
+ *     from the camera through the pixel centre hits the triangle's plane at z >= znear inside the triangle); triangles
+ *     wholly in front of znear, degenerate faces, faces with an index outside [0, V), repeated indices or non-finite
+ *     vertices render nothing;
+ *   - coverage is inclusive (a centre exactly on an edge is covered) and watertight: every edge function is the fp64
+ *     d . (P_lo x P_hi) of the edge's endpoints in ascending vertex-index order (times +-1), evaluated identically from
+ *     both faces sharing it, with d = ((u - cx) / fx, (v - cy) / fy, 1) and P the fp64 camera-space vertices;
+ *   - depth is the ray-plane intersection z = P0 . n / (d . n) in fp64 (perspective-correct), rounded to fp32 once;
+ *   - the min over fragments is an atomicMin on the fp32 bit pattern (positive floats order as uint32), so the maps do
+ *     not depend on arrival order and reruns are bitwise identical.
+ *   One thread per face loads its vertices once for all n_poses poses; triangles whose pixel range exceeds 256 pixels go
+ *   to a list (GS_MESH_DEPTH_LARGE_CAP entries in the workspace) that a second launch rasterises one workgroup per
+ *   (face, pose).  workspace: gs_mesh_depth_workspace_bytes().  H * W <= 2^24.
+ *
+ * gs_mesh_visibility: Mesher.point_masks (src/mesher.py:56-137) for points f32 [n,3] against one chunk of n_poses
+ * depth maps f32 [n_poses,H,W], w2c f32 [n_poses,4,4] = torch.inverse(c2w) in fp32.  Per frame, in fp32:
+ *   cam = w2c . [p, 1], z = cam_z + 1e-8, u = (fx cam_x + cx cam_z) / z, v = (fy cam_y + cy cam_z) / z;
+ *   in_frustum = 0 <= u <= W-1 && 0 <= v <= H-1 && z > 0; forecast_frustum likewise on the image grown by
+ *   r = forecast_radius pixels per side (r < 0 shrinks it);
+ *   d = grid_sample(depth, (u / (W-1) * 2 - 1, v / (H-1) * 2 - 1), padding_mode='border', align_corners=True) (bilinear,
+ *   clamped to the border, zero texels blended); front = d > 0 ? z < d + 0.05 : true;
+ *   seen |= in_frustum && front; forecast |= (in_frustum && front) || (forecast_frustum && front).
+ *   seen / forecast uint8 [n] are read and OR-ed into (zero them before the first chunk).  One thread per point, the pose
+ *   loop inside the kernel.  The fp32 sums of cam and uv are not torch's matmul order: decisions within a few ulps of a
+ *   bound may differ.
+ *
+ * gs_face_components: trimesh's mesh.split(only_watertight=False) as get_connected_mesh (src/mesher.py:139-153) uses
+ * it.  Faces i32 [F,3]; two faces are adjacent iff they share an edge (the same unordered pair of vertex indices); an
+ * edge with equal endpoints connects nothing; an edge of more than two faces connects all of them.  labels i32 [F] =
+ * the smallest face index of the face's component.  Edge -> smallest face in a device hash table (64-bit keys, linear
+ * probing), union by compare-and-swap hooking of the larger root under the smaller, then pointer jumping.  F <= 2^28;
+ * workspace: gs_face_components_workspace_bytes(F).
+ *
+ * gs_face_component_areas: from float64 vertices [V,3], faces, perm i32 [F] (the face order sorted by label, stable)
+ * and sorted_labels i32 [F] (labels[perm]): comp_area f64 [F] (comp_area[label] = the component's area, 0 at indices
+ * that are no label) and total f64 [1] = the sum of comp_area.  Face area 0.5 |(v1 - v0) x (v2 - v0)| in fp64; each
+ * component summed in ascending sorted position within 1024-face tiles, the tiles' partial sums in tile order, the
+ * total in a fixed strided-then-tree order: bitwise reproducible.  workspace: 16 bytes per face.
+ *
+ * gs_hull_extremes / gs_hull_prefilter: an exact interior-discard filter in front of the convex hull behind
+ * OrientedBoundingBox.compute_from_pointcloud (Open3D's create_from_points: PCA of the convex-hull vertices).
+ *   gs_hull_extremes: idx i32 [26] = for each of the 13 axis / face-diagonal / body-diagonal directions d, the point
+ *     maximising +d . p, then -d . p (fp64; ties to the lower index; -1 if no point has a finite value).
+ *     workspace: gs_hull_extremes_workspace_bytes(n).
+ *   gs_hull_prefilter: keep u8 [n] = 0 iff n_k . p + c_k < -margin for every plane k (planes f64 [n_planes,4], the
+ *     facets of the hull of those points as qhull writes them, outward normals), in fp64.  A point strictly inside the
+ *     hull of a subset of the cloud is never a vertex of the cloud's hull; margin absorbs the planes' rounding.    */
+#define GS_MESH_DEPTH_LARGE_CAP (1 << 20)
+size_t gs_mesh_depth_workspace_bytes(void);
+int gs_mesh_depth(const float* vertices, int n_vertices, const int* faces, int n_faces, const float* w2c, int n_poses,
+                  float fx, float fy, float cx, float cy, int height, int width, float znear, float zfar, float* depth,
+                  void* workspace, size_t workspace_bytes, gs_stream_t stream);
+int gs_mesh_visibility(const float* points, int n_points, const float* w2c, const float* depth, int n_poses, float fx,
+                       float fy, float cx, float cy, int height, int width, float forecast_radius, uint8_t* seen,
+                       uint8_t* forecast, gs_stream_t stream);
+size_t gs_face_components_workspace_bytes(int n_faces);
+int gs_face_components(const int* faces, int n_faces, int* labels, void* workspace, size_t workspace_bytes,
+                       gs_stream_t stream);
+int gs_face_component_areas(const double* vertices, const int* faces, int n_faces, const int* perm,
+                            const int* sorted_labels, double* comp_area, double* total, void* workspace,
+                            size_t workspace_bytes, gs_stream_t stream);
+size_t gs_hull_extremes_workspace_bytes(int n_points);
+int gs_hull_extremes(const float* points, int n_points, int* idx, void* workspace, size_t workspace_bytes,
+                     gs_stream_t stream);
+int gs_hull_prefilter(const float* points, int n_points, const double* planes, int n_planes, double margin,
+                      uint8_t* keep, gs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
