@@ -123,6 +123,12 @@ SIGNATURES = {
     "gs_hull_extremes_workspace_bytes": (c_size_t, [c_int]),
     "gs_hull_extremes": (c_int, [_P, c_int, _P, _P, c_size_t, _P]),
     "gs_hull_prefilter": (c_int, [_P, c_int, _P, c_int, ctypes.c_double, _P, _P]),
+    "gs_nn_cell_keys": (c_int, [_P, c_int, _P, _P, _P, _P]),
+    "gs_nn_grid_build": (c_int, [_P, c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "gs_nn_query_workspace_bytes": (c_size_t, [c_int]),
+    "gs_nn_query": (c_int, [_P, _P, _P, _P, c_int, _P, _P, _P, c_int, _P, ctypes.c_double, _P, _P, _P, c_size_t, _P]),
+    "gs_icp_moments_workspace_bytes": (c_size_t, [c_int]),
+    "gs_icp_moments": (c_int, [_P, c_int, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
 }
 
 

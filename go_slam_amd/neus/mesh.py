@@ -80,6 +80,15 @@ class Mesh:
         v = self.vertices[self.faces]
         return float(0.5 * np.linalg.norm(np.cross(v[:, 1] - v[:, 0], v[:, 2] - v[:, 0]), axis=1).sum())
 
+    def apply_transform(self, matrix):
+        """trimesh's apply_transform, in place in float64: v <- (M [v, 1])[:3] for a 4x4 M with last row (0, 0, 0, 1);
+        the winding flips when det M[:3,:3] < 0 so that normals keep pointing outward.  Returns self."""
+        M = np.asarray(matrix, dtype=np.float64).reshape(4, 4)
+        self.vertices = np.ascontiguousarray(self.vertices @ M[:3, :3].T + M[:3, 3])
+        if np.linalg.det(M[:3, :3]) < 0:
+            self.faces = np.ascontiguousarray(self.faces[:, ::-1])
+        return self
+
     def copy(self):
         return Mesh(self.vertices.copy(), self.faces.copy(),
                     None if self.vertex_colors is None else self.vertex_colors.copy())
@@ -109,3 +118,134 @@ class Mesh:
             fh.write(vrec.tobytes())
             fh.write(frec.tobytes())
         return path
+
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2",
+              "ushort": "u2", "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4",
+              "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
+
+
+def _ply_header(fh):
+    if fh.readline().strip() != b"ply":
+        raise ValueError("not a PLY file")
+    fmt, elements = None, []
+    while True:
+        line = fh.readline()
+        if not line:
+            raise ValueError("PLY header has no end_header")
+        words = line.decode("ascii", "replace").split()
+        if not words or words[0] in ("comment", "obj_info"):
+            continue
+        if words[0] == "end_header":
+            return fmt, elements
+        if words[0] == "format":
+            fmt = words[1]
+        elif words[0] == "element":
+            elements.append((words[1], int(words[2]), []))
+        elif words[0] == "property":
+            if words[1] == "list":      # (name, count type, item type)
+                elements[-1][2].append((words[4], _PLY_TYPES[words[2]], _PLY_TYPES[words[3]]))
+            else:
+                elements[-1][2].append((words[2], _PLY_TYPES[words[1]], None))
+
+
+def _ply_read_binary(fh, count, props, endian):
+    """One element of a binary PLY: {property: array}, list properties as lists of arrays (or a 2-D array when every
+    list has the same length)."""
+    if all(item is None for _, _, item in props):
+        dt = np.dtype([(n, endian + t) for n, t, _ in props])
+        rec = np.frombuffer(fh.read(dt.itemsize * count), dtype=dt, count=count)
+        return {n: rec[n] for n, _, _ in props}
+    if count == 0:
+        return {n: (np.zeros((0, 3), dtype=np.int64) if item else np.zeros(0)) for n, _, item in props}
+    # the common case first: every list has the length of the first record's
+    start = fh.tell()
+    fields, lens = [], []
+    head = fh.read(max(np.dtype(t).itemsize for _, t, _ in props) * 64 + 64)
+    fh.seek(start)
+    off = 0
+    for n, t, item in props:
+        if item is None:
+            fields.append((n, endian + t))
+            off += np.dtype(t).itemsize
+        else:
+            k = int(np.frombuffer(head[off:off + np.dtype(t).itemsize], dtype=endian + t)[0])
+            fields.append((n + "#n", endian + t))
+            fields.append((n, endian + item, (k,)))
+            off += np.dtype(t).itemsize + k * np.dtype(item).itemsize
+            lens.append(k)
+    dt = np.dtype(fields)
+    raw = fh.read(dt.itemsize * count)
+    if len(raw) == dt.itemsize * count:
+        rec = np.frombuffer(raw, dtype=dt, count=count)
+        if all((rec[n + "#n"] == k).all() for (n, _, item), k in zip([p for p in props if p[2]], lens)):
+            return {n: rec[n] for n, _, _ in props}
+    fh.seek(start)          # mixed list lengths: record by record
+    out = {n: [] for n, _, _ in props}
+    for _ in range(count):
+        for n, t, item in props:
+            size = np.dtype(t).itemsize
+            v = np.frombuffer(fh.read(size), dtype=endian + t)[0]
+            if item is None:
+                out[n].append(v)
+            else:
+                isz = np.dtype(item).itemsize
+                out[n].append(np.frombuffer(fh.read(isz * int(v)), dtype=endian + item))
+    return {n: (np.asarray(out[n]) if item is None else out[n]) for n, _, item in props}
+
+
+def _ply_read_ascii(fh, count, props, tokens):
+    out = {n: [] for n, _, _ in props}
+    for _ in range(count):
+        for n, t, item in props:
+            if item is None:
+                out[n].append(next(tokens))
+            else:
+                k = int(float(next(tokens)))
+                out[n].append(np.array([next(tokens) for _ in range(k)], dtype=np.float64).astype(item))
+    return {n: (np.asarray(out[n], dtype=np.float64).astype(t) if item is None else out[n]) for n, t, item in props}
+
+
+def _triangles(lists):
+    """Face lists -> int64 [F,3]; polygons with more than three vertices are fan-triangulated (0, i, i+1)."""
+    if isinstance(lists, np.ndarray) and lists.ndim == 2:
+        k = lists.shape[1]
+        if k < 3:
+            return np.zeros((0, 3), dtype=np.int64)
+        a = lists.astype(np.int64)
+        return np.ascontiguousarray(np.stack([np.stack([a[:, 0], a[:, i], a[:, i + 1]], 1) for i in range(1, k - 1)],
+                                             1).reshape(-1, 3))
+    tris = []
+    for f in lists:
+        f = np.asarray(f, dtype=np.int64)
+        for i in range(1, len(f) - 1):
+            tris.append((f[0], f[i], f[i + 1]))
+    return np.asarray(tris, dtype=np.int64).reshape(-1, 3)
+
+
+def load_mesh(path):
+    """A PLY file as a Mesh, with trimesh.load_mesh(path, process=False) semantics (no merging, no reordering): ASCII or
+    binary of either endianness; float or double x, y, z; other vertex properties skipped except red, green, blue (read
+    as colours); faces from `vertex_indices` or `vertex_index` lists of any count and index types, fan-triangulated."""
+    with open(path, "rb") as fh:
+        fmt, elements = _ply_header(fh)
+        if fmt not in ("ascii", "binary_little_endian", "binary_big_endian"):
+            raise ValueError(f"load_mesh: unsupported PLY format {fmt!r}")
+        tokens = iter(fh.read().split()) if fmt == "ascii" else None
+        data = {}
+        for name, count, props in elements:
+            if fmt == "ascii":
+                data[name] = _ply_read_ascii(fh, count, props, tokens)
+            else:
+                data[name] = _ply_read_binary(fh, count, props, "<" if fmt == "binary_little_endian" else ">")
+    vert = data.get("vertex", {})
+    if not all(k in vert for k in "xyz"):
+        raise ValueError("load_mesh: the vertex element has no x, y, z")
+    vertices = np.stack([np.asarray(vert[k], dtype=np.float64) for k in "xyz"], 1)
+    colors = None
+    if all(k in vert for k in ("red", "green", "blue")):
+        colors = np.stack([np.asarray(vert[k]).astype(np.uint8) for k in ("red", "green", "blue")], 1)
+    face = data.get("face", {})
+    key = "vertex_indices" if "vertex_indices" in face else ("vertex_index" if "vertex_index" in face else None)
+    faces = _triangles(face[key]) if key else np.zeros((0, 3), dtype=np.int64)
+    return Mesh(vertices, faces, colors)

@@ -11,17 +11,17 @@
 Contracts: include/goslam_neus.h; tests/cull_restatement.py restates them on the CPU.  Deliberate differences from the
 reference: exact fp32 depth with inclusive coverage instead of a 24-bit GL depth buffer; culled meshes keep
 the input's face and vertex order (face masks) instead of being regrouped by component; no component above the area
-threshold gives an empty Mesh; align_mesh / eval_mesh are not run.
+threshold gives an empty Mesh.  align_mesh / eval_mesh at the end of a run: mesh_eval.py.
 """
 import copy
 import os
-import warnings
 
 import numpy as np
 import torch
 
 from .. import _lib
-from .mesh import Mesh
+from .mesh import Mesh, load_mesh
+from .mesh_eval import align_mesh, eval_mesh
 
 ZNEAR = 0.001
 HULL_MARGIN = 1e-9          # relative margin of the interior test (qhull's plane rounding is far below it)
@@ -239,9 +239,8 @@ class OrientedBoundingBox(torch.nn.Module):
 
 
 class Mesher(object):
-    """src/mesher.py `Mesher` with the same constructor, attributes and flow; meshing, culling and the bounding box on the
-    GPU.  align_mesh / eval_mesh (ICP, surface sampling, KD-tree metrics) are not run: when the ground-truth mesh exists
-    at the end of a run a warning says so."""
+    """src/mesher.py `Mesher` with the same constructor, attributes and flow; meshing, culling, the bounding box and, at
+    the end of a run with a ground-truth PLY, align_mesh / eval_mesh (mesh_eval.py) on the GPU."""
 
     def __init__(self, cfg, args, slam, points_batch_size=5e5):
         self.points_batch_size = int(points_batch_size)
@@ -413,8 +412,15 @@ class Mesher(object):
                                                       mesh_out_file=mesh_out_file)
 
             if the_end and os.path.exists(self.gt_mesh_path) and self.gt_mesh_path.find('.ply') > -1:
-                warnings.warn(f"Mesher: ground-truth mesh {self.gt_mesh_path} found, but align_mesh / eval_mesh are not "
-                              "part of this package: the mesh is neither aligned nor evaluated")
+                gt_mesh = load_mesh(self.gt_mesh_path)
+                aligned_mesh, transformation = align_mesh(cull_mesh, gt_mesh, threshold=0.1, trans_init=trans_init,
+                                                          return_transformation=True)
+                aligned_mesh.export(f'{self.output}/mesh/aligned_mesh.ply')
+                forecast_mesh.apply_transform(transformation)
+                forecast_mesh.export(f'{self.output}/mesh/forecast_aligned_mesh.ply')
+                if self.eval_rec:
+                    eval_mesh(forecast_mesh, gt_mesh, N3d=self.n_points_to_eval, dist_th=self.mesh_threshold_to_eval,
+                              out_path=f'{self.output}/metrics_mesh.txt')
 
             if self.verbose:
                 print("\nINFO: Save mesh at {}!\n".format(mesh_out_file))

@@ -383,6 +383,52 @@ int gs_hull_extremes(const float* points, int n_points, int* idx, void* workspac
 int gs_hull_prefilter(const float* points, int n_points, const double* planes, int n_planes, double margin,
                       uint8_t* keep, gs_stream_t stream);
 
+/* Mesh evaluation (Mesher.__call__ at the end of a run, reference src/mesher.py:309-327): exact nearest neighbours
+ * between fp64 point clouds -- the two cKDTree passes of eval_mesh (src/mesher.py:390-421) and the hybrid search of the
+ * Open3D point-to-point ICP behind align_mesh (src/mesher.py:339-357) -- and the moments of an ICP correspondence set.
+ *
+ * Contract of a query (gs_nn_query): reference points R f64 [N,3], queries Q f64 [M,3], optional transform f64 [4,4]
+ * (row-major, device) applied to each query as q'_r = ((T[r,0] q_x + T[r,1] q_y) + T[r,2] q_z) + T[r,3];
+ *   d2 = dx*dx + dy*dy + dz*dz (left to right, no contraction), index = the nearest point of R, the smallest index on
+ *   equal d2.  max_distance >= 0: Open3D's hybrid search with one neighbour: the nearest point is returned iff
+ *   d2 < max_distance^2 (strict, as FLANN's radius result set), otherwise index -1 and d2 = +inf.  max_distance < 0:
+ *   no limit.  A query with a non-finite coordinate gets index -1, d2 = +inf.  Exact, so reruns are bitwise identical.
+ *
+ * Grid: a uniform grid over R's bounding box, grid_host f64 [5] = (lo_x, lo_y, lo_z, h, scale) and dims_host i32 [3]
+ * (nx, ny, nz; nx ny nz <= GS_NN_MAX_CELLS), scale = the largest |coordinate| of the box + h.  The cell of a point is
+ * floor((p - lo) / h) per axis (clamped to the grid for R), key = (cz ny + cy) nx + cx.
+ *   gs_nn_cell_keys: keys i32 [N].
+ *   gs_nn_grid_build: from sorted_keys i32 [N] and perm i64 [N] (a stable sort of the keys, so ascending index within
+ *     a cell): cell_start i32 [nx ny nz + 1] (the first sorted position of each cell), sorted_points f64 [N,3] =
+ *     points[perm], sorted_index i32 [N] = perm.
+ *   gs_nn_query: one lane per query visits rings of cells of growing Chebyshev radius around the query's cell and stops
+ *     when the best d2 is below the squared distance to the unvisited region, that distance first reduced by a slack
+ *     1e-9 (scale + |q|_1) that dwarfs fp64 rounding (so rounding can never end a search early); with max_distance it
+ *     also stops once that bound reaches max_distance^2.  A query that would visit more than GS_NN_CELL_BUDGET cells is
+ *     put on a list that a brute-force launch resolves (R streamed through LDS, ascending index, strict <): the work per
+ *     query is bounded by GS_NN_CELL_BUDGET cells plus N points.  workspace: gs_nn_query_workspace_bytes(M); its first
+ *     int32 is the number of queries that fell back.  No host synchronisation.
+ *
+ * gs_icp_moments: over the correspondences i (index[i] >= 0) of source f64 [n,3] (transformed as above when transform
+ * != NULL) and target f64 [*,3]: moments f64 [17] = count, sum d2, source centroid [3], target centroid [3] (0 when
+ * the count is 0), then sum_i (t_i - t_mean)(s_i - s_mean)^T row-major [3,3] (row = target axis).  Two passes (the
+ * sums, then the centred products), each summed within tiles of 2048 correspondences (per thread in ascending order,
+ * then a fixed tree) and the tiles in tile order: bitwise reproducible.  workspace: gs_icp_moments_workspace_bytes(n). */
+#define GS_NN_MAX_CELLS (1 << 25)
+#define GS_NN_CELL_BUDGET 16384
+int gs_nn_cell_keys(const double* points, int n_points, const double* grid_host, const int* dims_host, int* keys,
+                    gs_stream_t stream);
+int gs_nn_grid_build(const double* points, int n_points, const int* sorted_keys, const int64_t* perm,
+                     const int* dims_host, int* cell_start, double* sorted_points, int* sorted_index, gs_stream_t stream);
+size_t gs_nn_query_workspace_bytes(int n_queries);
+int gs_nn_query(const double* points, const double* sorted_points, const int* sorted_index, const int* cell_start,
+                int n_points, const double* grid_host, const int* dims_host, const double* queries, int n_queries,
+                const double* transform, double max_distance, double* d2, int* index, void* workspace,
+                size_t workspace_bytes, gs_stream_t stream);
+size_t gs_icp_moments_workspace_bytes(int n_source);
+int gs_icp_moments(const double* source, int n_source, const double* transform, const double* target, const int* index,
+                   const double* d2, double* moments, void* workspace, size_t workspace_bytes, gs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
