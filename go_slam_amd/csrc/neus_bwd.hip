@@ -612,6 +612,235 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void n
   }
 }
 
+// ---- ray gradients (mapping.BA): dL / d rays_o and dL / d rays_d.  A pass of its own after the backward, launched only
+// when ray gradients are requested (the backward above is untouched by the option).  One lane per sample point forms
+//   dL/dx = [ u_p + 1/2 sum_lf u_lf d enc_lf / d view                          (a) first order: u = W_sdf^T [dsdf, dfeat]
+//             + 1/4 sum_lf g_lf H_lf^T dG                                      (b) second order through d sdf / d x
+//           ] * inside * 2 / span
+//           + B (dL/demb * cos(x B))                                           (c) colour embedding sin(x B)
+// and dL/d dir = dc * g where true_cos < 0 (d) -- the NeuS alpha's cos term.  H_lf is the trilinear interpolation's mixed
+// second derivative (zero diagonal; tiny-cuda-nn's backward_input_backward_input), read from the 8 corner values gathered
+// here (the forward's aux record holds d enc / d x, not the corners).  Per point the kernel writes
+// [dL/dx, z_mid dL/dx + dL/d dir]; ray_sum6_kernel adds a ray's samples in a fixed order (no float atomics).
+__global__ __launch_bounds__(256) void neus_point_raygrad_kernel(BwdArgs A, gs_grid_meta m, float* __restrict__ pg) {
+  typedef const __attribute__((address_space(4))) float* cfp;
+  cfp cB = (cfp)A.color_B;
+  cfp W = (cfp)A.sdf_w;
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  const int np = A.n * A.s;
+  if (idx >= np) return;
+  const int i = idx, ray = i / A.s;
+  const uint8_t mk = A.mask[i];
+  const float dist = A.dists[i], zv = A.z_vals[i], sdf = A.sdf[i];
+  const float d_sdf_in = A.d_sdf[i], da_in = A.d_alpha[i], gerr_ray = A.d_gerr_ray[ray];
+  float g[3], dg_in[3], dir[3], org[3];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    g[d] = A.grad[i * 3 + d];
+    dg_in[d] = A.d_grad[i * 3 + d];
+    dir[d] = A.rays_d[ray * 3 + d];
+    org[d] = A.rays_o[ray * 3 + d];
+  }
+  const float inv_s_ = A.inv_s_dev ? *A.inv_s_dev : A.inv_s;
+  float dxh[40];
+  load_dx40(A, i, 32, dxh);
+  const float live = mk != 0 ? 1.0f : 0.0f;
+  const float zm = zv + dist / 2.0f;
+  float pt[3];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) pt[d] = org[d] + dir[d] * zm;
+  // total dL/dsdf and dL/dg exactly as neus_point_bwd_kernel forms them; plus dL/d dir of the cos term
+  float d_sdf = d_sdf_in * live, dg[3], ddir[3] = {0.f, 0.f, 0.f};
+  const float gn = sqrtf((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]);
+  const float eik = (gn > 0.f) ? gerr_ray * 2.0f * (gn - 1.0f) / gn : 0.0f;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) dg[d] = (dg_in[d] + eik * g[d] + dxh[1 + d]) * live;
+  {
+    const float da = da_in * live;
+    const float cosv = (dir[0] * g[0] + dir[1] * g[1]) + dir[2] * g[2];
+    const float c = -fmaxf(-cosv, 0.0f);
+    const float est_next = sdf + c * dist / 2.0f, est_prev = sdf - c * dist / 2.0f;
+    const float p = 1.0f / (1.0f + expf(-(est_prev * inv_s_)));
+    const float q = 1.0f / (1.0f + expf(-(est_next * inv_s_)));
+    const float raw = (p - q + 1e-5f) / (p + 1e-5f);
+    if (da != 0.0f && raw >= 0.0f && raw <= 1.0f) {
+      const float dp = da * q / ((p + 1e-5f) * (p + 1e-5f));
+      const float dq = -da / (p + 1e-5f);
+      const float dprev = dp * p * (1.0f - p), dnext = dq * q * (1.0f - q);
+      d_sdf += (dprev + dnext) * inv_s_;
+      const float dc = (dnext - dprev) * inv_s_ * dist / 2.0f;
+      if (cosv < 0.0f) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) { dg[d] += dc * dir[d]; ddir[d] = dc * g[d]; }
+      }
+    }
+  }
+  float view[3], dG[3], jac[3];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    const float span = A.bound[2 * d + 1] - A.bound[2 * d];
+    float qn = (pt[d] - A.bound[2 * d]) / span * 2.0f - 1.0f;
+    const float inside = (qn >= -1.0f && qn <= 1.0f) ? 1.0f : 0.0f;
+    qn = fminf(fmaxf(qn, -1.0f), 1.0f);
+    view[d] = (qn + 1.0f) / 2.0f;
+    jac[d] = inside * 2.0f / span;                 // d p / d x (the clamp passes the gradient on [-1, 1])
+    dG[d] = dg[d] * jac[d];
+  }
+  float dov[32];
+  dov[0] = d_sdf;
+#pragma unroll
+  for (int o = 1; o < 32; ++o) dov[o] = dxh[4 + (o - 1)] * live;
+  float dp[3];                                     // (a) the xyz passthrough columns of the SDF linear layer
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    float a = 0.f;
+#pragma unroll
+    for (int o = 0; o < 32; ++o) a = fmaf(dov[o], W[o * 35 + d], a);
+    dp[d] = a;
+  }
+  float dv[3] = {0.f, 0.f, 0.f};                   // dL / d view
+#pragma unroll 1
+  for (int l = 0; l < GS_GRID_LEVELS; ++l) {
+    const float scale = m.scale[l];
+    float f[3];
+    uint32_t gi[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      const float pos = fmaf(scale, view[d], 0.5f);
+      const float fl = floorf(pos);
+      gi[d] = (uint32_t)(int)fl;
+      f[d] = pos - fl;
+    }
+    uint32_t cidx[8];
+    grid_corners(m, l, gi, cidx);
+    const size_t off = (size_t)m.offset[l];
+    float v[8][2];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      const uint32_t raw = *reinterpret_cast<const uint32_t*>(A.grid + (off + cidx[c]) * 2);
+      v[c][0] = (float)__builtin_bit_cast(_Float16, (uint16_t)(raw & 0xffffu));
+      v[c][1] = (float)__builtin_bit_cast(_Float16, (uint16_t)(raw >> 16));
+    }
+    float de[2] = {0.f, 0.f};
+#pragma unroll
+    for (int o = 0; o < 32; ++o) {
+      de[0] = fmaf(dov[o], W[o * 35 + 3 + 2 * l], de[0]);
+      de[1] = fmaf(dov[o], W[o * 35 + 4 + 2 * l], de[1]);
+    }
+    const float gw[2] = {(float)(_Float16)W[3 + 2 * l], (float)(_Float16)W[4 + 2 * l]};
+#pragma unroll
+    for (int ft = 0; ft < 2; ++ft) {
+      // first derivatives d enc / d view_gd (as the backward forms dy)
+#pragma unroll
+      for (int gd = 0; gd < 3; ++gd) {
+        const int o0 = (gd == 0) ? 1 : 0, o1 = (gd == 2) ? 1 : 2;
+        float a = 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          float w = scale;
+          w = w * ((k & 1) ? f[o0] : (1.0f - f[o0]));
+          w = w * ((k & 2) ? f[o1] : (1.0f - f[o1]));
+          const int cl = ((k & 1) << o0) | (((k >> 1) & 1) << o1);
+          a = fmaf(w, v[cl | (1 << gd)][ft] - v[cl][ft], a);
+        }
+        dv[gd] = fmaf(de[ft], a, dv[gd]);
+      }
+      // mixed second derivatives H[d][e] = scale^2 sum_t w_t (v_11 - v_10 - v_01 + v_00), t the third axis
+      float H[3];                                  // H01, H02, H12
+#pragma unroll
+      for (int pr = 0; pr < 3; ++pr) {
+        const int d = pr == 2 ? 1 : 0, e = pr == 0 ? 1 : 2, t = 3 - d - e;
+        float h = 0.f;
+#pragma unroll
+        for (int bt = 0; bt < 2; ++bt) {
+          const int ct = bt << t;
+          const float x = ((v[ct | (1 << d) | (1 << e)][ft] - v[ct | (1 << d)][ft]) - v[ct | (1 << e)][ft]) + v[ct][ft];
+          h = fmaf(bt ? f[t] : (1.0f - f[t]), x, h);
+        }
+        H[pr] = h * scale * scale;
+      }
+      const float q = 0.5f * gw[ft];
+      dv[0] = fmaf(q, dG[1] * H[0] + dG[2] * H[1], dv[0]);
+      dv[1] = fmaf(q, dG[0] * H[0] + dG[2] * H[2], dv[1]);
+      dv[2] = fmaf(q, dG[0] * H[1] + dG[1] * H[2], dv[2]);
+    }
+  }
+  float dx[3];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) dx[d] = (dp[d] + 0.5f * dv[d]) * jac[d];
+  {   // (c) the colour embedding: d x_d += sum_j d emb_j cos(arg_j) B[d][j]
+    float dxe[40];
+    load_dx40(A, i, 0, dxe);
+#pragma unroll
+    for (int c = 0; c < 33; ++c) {
+      const float arg = (pt[0] * cB[c] + pt[1] * cB[33 + c]) + pt[2] * cB[66 + c];
+      const float da = dxe[c] * emb_cos(arg) * live;
+      dx[0] = fmaf(da, cB[c], dx[0]);
+      dx[1] = fmaf(da, cB[33 + c], dx[1]);
+      dx[2] = fmaf(da, cB[66 + c], dx[2]);
+    }
+  }
+  float* o = pg + (size_t)i * 6;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    o[d] = dx[d];
+    o[3 + d] = fmaf(zm, dx[d], ddir[d]);
+  }
+}
+
+// one wave per ray: the ray's s rows of 6 floats summed in a fixed order (lane k: samples k, k + 64; then the wave's
+// butterfly) -- reruns are bitwise identical
+__global__ __launch_bounds__(256) void ray_sum6_kernel(const float* __restrict__ pg, float* __restrict__ out, int n, int s) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= n) return;
+  float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int k = lane; k < s; k += 64) {
+    const float* row = pg + ((size_t)r * s + k) * 6;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) acc[c] += row[c];
+  }
+#pragma unroll
+  for (int c = 0; c < 6; ++c) {
+    const float t = gs_wave_sum(acc[c]);
+    if (lane == 0) out[(size_t)r * 6 + c] = t;
+  }
+}
+
+// per visit_list entry: dL/dR[i][j] = sum_r dL/d rays_d[r][i] dirs[r][j], dL/dt = sum_r dL/d rays_o[r] over the entry's
+// segment of rays; one workgroup per entry, strided per-thread sums, then the waves' butterflies and a fixed 4-way sum
+__global__ __launch_bounds__(256) void pose_grad_reduce_kernel(const float* __restrict__ rg, const float* __restrict__ dirs,
+                                                               const int* __restrict__ seg, float* __restrict__ out) {
+  __shared__ float part[4][12];
+  const int e = blockIdx.x;
+  const int r0 = seg[e], r1 = seg[e + 1];
+  float acc[12];
+#pragma unroll
+  for (int c = 0; c < 12; ++c) acc[c] = 0.f;
+  for (int r = r0 + (int)threadIdx.x; r < r1; r += 256) {
+    const float* g = rg + (size_t)r * 6;
+    const float dd[3] = {g[3], g[4], g[5]};
+    const float dc[3] = {dirs[(size_t)r * 3], dirs[(size_t)r * 3 + 1], dirs[(size_t)r * 3 + 2]};
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+#pragma unroll
+      for (int b = 0; b < 3; ++b) acc[3 * a + b] = fmaf(dd[a], dc[b], acc[3 * a + b]);
+      acc[9 + a] += g[a];
+    }
+  }
+  const int w = threadIdx.x >> 6;
+#pragma unroll
+  for (int c = 0; c < 12; ++c) {
+    const float t = gs_wave_sum(acc[c]);
+    if ((threadIdx.x & 63) == 0) part[w][c] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x < 12) {
+    const int c = threadIdx.x;
+    out[(size_t)e * 12 + c] = (part[0][c] + part[1][c]) + (part[2][c] + part[3][c]);
+  }
+}
+
 // pass 2 of bin-and-reduce: one workgroup per (hashed level, bin); see the file header
 __device__ __forceinline__ long long fix24(uint32_t h) {       // fp16 bits -> value * 2^24, exact (|v| <= 65504 < 2^16)
   const float v = fminf(fmaxf((float)__builtin_bit_cast(_Float16, (uint16_t)h), -65504.0f), 65504.0f);   // (inf: saturate)
@@ -892,4 +1121,45 @@ extern "C" int gs_neus_backward_points_binned(const float* rays_o, const float* 
                               mask, d_alpha, d_sdf, d_grad, dX, dx_dtype, dx_scale, d_gerr_ray, grid_grad, GS_F16,
                               grid_grad_scale, d_out, lin_in, dw0, d_arg, pts, row_dtype, row_scale, row_stride, d_inv_s, n,
                               s, bin_ws, bin_ws_bytes, sdf_wt, enc_aux, stream);
+}
+
+extern "C" int gs_neus_backward_raygrad(const float* rays_o, const float* rays_d, const float* z_vals, const float* dists,
+                                        const void* grid, const float* sdf_w, const float* color_B, float inv_s,
+                                        const float* inv_s_dev, const float* bound_host, const float* sdf, const float* grad,
+                                        const uint8_t* mask, const float* d_alpha, const float* d_sdf, const float* d_grad,
+                                        const void* dX, int dx_dtype, float dx_scale, const float* d_gerr_ray,
+                                        float* point_ws, float* d_rays, int n, int s, gs_stream_t stream) {
+  GS_REQUIRE(rays_o && rays_d && z_vals && dists && grid && sdf_w && color_B && bound_host && sdf && grad && mask &&
+                 d_alpha && d_sdf && d_grad && dX && d_gerr_ray && point_ws && d_rays,
+             "neus_backward_raygrad: null pointer");
+  GS_REQUIRE(dx_dtype == GS_F32 || dx_dtype == GS_F16, "neus_backward_raygrad: dX dtype f32 or f16");
+  GS_REQUIRE(dx_scale > 0.0f, "neus_backward_raygrad: dx_scale must be positive");
+  GS_REQUIRE(n >= 0 && s > 0 && (long long)n * s < (1ll << 31), "neus_backward_raygrad: bad shape");
+  if (n == 0) return GS_OK;
+  BwdArgs A = {};
+  A.rays_o = rays_o; A.rays_d = rays_d; A.z_vals = z_vals; A.dists = dists;
+  A.grid = (const _Float16*)grid; A.sdf_w = sdf_w; A.color_B = color_B; A.inv_s = inv_s; A.inv_s_dev = inv_s_dev;
+  for (int k = 0; k < 6; ++k) A.bound[k] = bound_host[k];
+  A.sdf = sdf; A.grad = grad; A.mask = mask; A.d_alpha = d_alpha; A.d_sdf = d_sdf; A.d_grad = d_grad; A.dX = dX;
+  A.d_gerr_ray = d_gerr_ray;
+  A.dx16 = dx_dtype == GS_F16; A.dx_inv_scale = 1.0f / dx_scale;
+  A.n = n; A.s = s;
+  const gs_grid_meta m = host_meta();
+  GS_TIMING_PRE();
+  neus_point_raygrad_kernel<<<gs_cdiv(n * s, 256), 256, 0, (hipStream_t)stream>>>(A, m, point_ws);
+  GS_CHECK_LAUNCH("neus_backward_raygrad");
+  ray_sum6_kernel<<<gs_cdiv(n, 4), 256, 0, (hipStream_t)stream>>>(point_ws, d_rays, n, s);
+  GS_CHECK_LAUNCH("neus_ray_sum6");
+  return GS_OK;
+}
+
+extern "C" int gs_pose_grad_reduce(const float* ray_grad, const float* dirs, const int* seg, int n_entries, float* out,
+                                   gs_stream_t stream) {
+  GS_REQUIRE(ray_grad && dirs && seg && out, "pose_grad_reduce: null pointer");
+  GS_REQUIRE(n_entries >= 0, "pose_grad_reduce: bad shape");
+  if (n_entries == 0) return GS_OK;
+  GS_TIMING_PRE();
+  pose_grad_reduce_kernel<<<(unsigned)n_entries, 256, 0, (hipStream_t)stream>>>(ray_grad, dirs, seg, out);
+  GS_CHECK_LAUNCH("pose_grad_reduce");
+  return GS_OK;
 }

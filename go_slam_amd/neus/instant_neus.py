@@ -298,9 +298,12 @@ class InstantNeuS(nn.Module):
         n, s = z_vals.shape
         var, inv_s = self._inv_s()
         f32 = dict(dtype=torch.float32, device=dev)
-        if self._needs_grad():
+        ray_grad = torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad)
+        if self._needs_grad() or ray_grad:
+            # rays that require grad stay attached: the backward then also returns dL/d rays_o, dL/d rays_d (mapping.BA)
+            ray = (lambda t: t.float().contiguous()) if ray_grad else (lambda t: t.detach().float().contiguous())
             color, depth, dvar, normal, wsum, sdf, gerr, zmid = _NeusRenderFn.apply(
-                self, rays_o.detach().float().contiguous(), rays_d.detach().float().contiguous(),
+                self, ray(rays_o), ray(rays_d),
                 z_vals.detach().float().contiguous(), dists.detach().float().contiguous(),
                 net.encoding.encoding.params, net.sdf_layer.weight, net.sdf_layer.bias, self.color_network._B,
                 self.color_network.network.params, self.variance_network.variance)
@@ -438,19 +441,27 @@ class _NeusRenderFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_color, d_depth, d_dvar, d_normal, d_wsum, d_sdf, d_gerr, _d_zmid):
+        want_rays = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        n = ctx.inputs[0].shape[0]
+        d_rays = torch.empty(n, 6, dtype=torch.float32, device=ctx.inputs[0].device) if want_rays else None
         g = _neus_backward_raw(ctx.model, ctx.saved, ctx.inputs, ctx.inv_s, ctx.var,
-                               d_color, d_depth, d_dvar, d_normal, d_wsum, d_sdf, d_gerr)
+                               d_color, d_depth, d_dvar, d_normal, d_wsum, d_sdf, d_gerr, ray_grad_out=d_rays)
         grid_acc, gscale = g["grid_acc"], g["grid_scale"]
         grid_grad = grid_acc.float().mul_(1.0 / gscale) if grid_acc.dtype == torch.float16 else grid_acc
-        return (None, None, None, None, None, grid_grad, g["sdf_w"], g["sdf_b"], g["cB"], g["mlp"], g["var"].reshape(()))
+        d_o = d_rays[:, :3] if want_rays and ctx.needs_input_grad[1] else None
+        d_d = d_rays[:, 3:] if want_rays and ctx.needs_input_grad[2] else None
+        return (None, d_o, d_d, None, None, grid_grad, g["sdf_w"], g["sdf_b"], g["cB"], g["mlp"], g["var"].reshape(()))
 
 
 def _neus_backward_raw(model, S, inputs, inv_s, var, d_color, d_depth, d_dvar, d_normal, d_wsum, d_sdf, d_gerr,
-                       inv_s_dev=None, var_dev=None, grid_acc_out=None, raw_dense=None, after_table=None):
+                       inv_s_dev=None, var_dev=None, grid_acc_out=None, raw_dense=None, after_table=None,
+                       ray_grad_out=None):
     """The HIP backward of the fused renderer: upstream gradients of the ray outputs -> gradients of every trained
     parameter.  Returns a dict: grid_acc (the raw table gradient: fp32, or tiny-cuda-nn's loss-scaled fp16 form with
     `grid_scale`), sdf_w, sdf_b, cB, mlp, var (fp32).  Used by the autograd Function above and, without any autograd
-    graph, by the fused mapper step (neus/mapper.py)."""
+    graph, by the fused mapper step (neus/mapper.py).  `ray_grad_out` (fp32 [n, 6], optional): also the ray gradients
+    [dL/d rays_o | dL/d rays_d] (gs_neus_backward_raygrad, a launch pair of its own after the point backward; without it
+    the launch sequence is exactly the one without ray gradients)."""
     rays_o, rays_d, z_vals, dists, sdf, zmid = inputs
     dev = rays_o.device
     n, s = z_vals.shape
@@ -539,6 +550,17 @@ def _neus_backward_raw(model, S, inputs, inv_s, var, d_color, d_depth, d_dvar, d
                                            d_arg.data_ptr(), pts.data_ptr(), 0, LS, 160, _lib.ptr(d_invs), n, s,
                                            _lib.ptr(S.get("enc_aux")), st)
     _lib.check(rc, "InstantNeuS.backward(points)")
+    if ray_grad_out is not None:
+        assert ray_grad_out.shape == (n, 6) and ray_grad_out.dtype == torch.float32 and ray_grad_out.is_contiguous()
+        pws = torch.empty(np_, 6, **f32)
+        with torch.cuda.device(dev):
+            rc = L.gs_neus_backward_raygrad(
+                _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(z_vals), _lib.ptr(dists), _lib.ptr(S["grid"]),
+                _lib.ptr(S["sdf_w"]), _lib.ptr(S["cB"]), float(inv_s), _lib.ptr(inv_s_dev), bh, _lib.ptr(sdf.contiguous()),
+                _lib.ptr(S["grad"]), _lib.ptr(S["mask"]), _lib.ptr(d_alpha), _lib.ptr(d_sdf), _lib.ptr(d_grad),
+                _lib.ptr(dX), 0, LS, _lib.ptr(d_gerr.reshape(-1).contiguous()), _lib.ptr(pws), _lib.ptr(ray_grad_out),
+                n, s, st)
+        _lib.check(rc, "InstantNeuS.backward(rays_o, rays_d)")
     if after_table is not None:     # the table gradient is complete: a sharded step starts its reduce-scatter here, under
         after_table()               # the Gram / post kernels that follow (neus/mapper.py)
     gram = torch.empty(L.gs_map_gram_blocks(np_pad), 40, 160, **f32)

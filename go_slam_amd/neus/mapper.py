@@ -133,6 +133,7 @@ class FlatAdamW:
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
         self.hyper = dict(lr16=grid_lr, lr32=net_lr, b1=betas[0], b2=betas[1], eps=eps, wd=weight_decay, max_norm=max_norm)
         self.steps = 0
+        self.extra_groups = []              # param_groups of other optimisers shown here (mapping.BA's camera group)
         self.overlap_gather = True          # world > 1: the all-gather of the updated table is waited for by its next reader
         self._gather_wait = None
         self._rs_wait = None                # world > 1: the reduce-scatter started under the backward's last kernels
@@ -142,7 +143,8 @@ class FlatAdamW:
     # the reference's mapper scales its learning rates per iteration (src/mapping.py: lr_factor) through param_groups
     @property
     def param_groups(self):
-        return [{"name": "network", "lr": self.hyper["lr32"]}, {"name": "volume", "lr": self.hyper["lr16"]}]
+        return ([{"name": "network", "lr": self.hyper["lr32"]}, {"name": "volume", "lr": self.hyper["lr16"]}]
+                + list(self.extra_groups))
 
     def set_lr(self, net_lr=None, grid_lr=None):
         if net_lr is not None:
@@ -339,7 +341,8 @@ class MapTrainer:
             raise RuntimeError("MapTrainer: model.realtime_bound must be a contiguous fp32 buffer on the rays' device")
         return rb
 
-    def _local_gradients(self, rays_o, rays_d, rays_color, rays_depth, perturb_rand, counts, bufs=None, after_table=None):
+    def _local_gradients(self, rays_o, rays_d, rays_color, rays_depth, perturb_rand, counts, bufs=None, after_table=None,
+                         ray_grad_out=None):
         """THIS RANK's rays: sample + forward + loss kernel + HIP backward, no autograd graph, no collective, no host
         sync.  `counts` = [valid rays, rays, max depth] over ALL ranks (device fp32[3]) or None (single rank: computed
         here).  Leaves the loss-scaled fp16 table gradient in flat.G16, the dense gradients in flat.g32[:nd] and this
@@ -384,7 +387,8 @@ class MapTrainer:
         _lib.check(rc, "mapping_loss")
         g = _neus_backward_raw(model, saved, (rays_o, rays_d, z_vals, dists, sdf, zmid), 0.0, 0.0,
                                d_color, d_depth, None, None, None, d_sdf, B["d_gerr"][:n], inv_s_dev=inv_s_dev,
-                               var_dev=var_dev, grid_acc_out=flat.grad_table(), raw_dense=B, after_table=after_table)
+                               var_dev=var_dev, grid_acc_out=flat.grad_table(), raw_dense=B, after_table=after_table,
+                               ray_grad_out=ray_grad_out)
         gram, part = g["gram"], g["mlp_partial"]
         with torch.cuda.device(dev):
             _lib.check(L.gs_map_step_post(_lib.ptr(gram), gram.shape[0], 1.0 / float(g["loss_scale"]), _lib.ptr(part),
@@ -549,6 +553,43 @@ class MapTrainer:
             ent["tail"].replay()
             flat.step(ent["inv_scale"], prepped=True)
         return self._global_loss()
+
+    def step_ray_grad(self, rays_o, rays_d, rays_color, rays_depth, perturb_rand=None):
+        """One joint iteration that ALSO returns the ray gradients: (loss, d_rays fp32 [n, 6] = [dL/d rays_o | dL/d
+        rays_d]) -- what mapping.BA chains into the camera poses.  The network update is the one `step` makes.  Runs
+        eagerly, never from a captured graph: it serves only the visit iterations of mapper calls with camera refinement
+        on, whose batch sizes are those of the BA-off step, so a second set of graphs per size would double the graph
+        memory (the 32768-ray step's binned queues alone are 1.9 GB) for ~65 launches' host time per iteration
+        (DESIGN.md 14).  Single GPU only: a sharded step would need its ray gradients gathered back."""
+        if self.world > 1 or self.sharded:
+            raise NotImplementedError("MapTrainer.step_ray_grad: ray gradients (mapping.BA) are not supported on a "
+                                      "sharded mapper (world > 1)")
+        n = rays_o.shape[0]
+        f32 = dict(dtype=torch.float32, device=rays_o.device)
+        d_rays = torch.zeros(n, 6, **f32)
+        if not self.fused:
+            rays_o = rays_o.detach().float().requires_grad_(True)
+            rays_d = rays_d.detach().float().requires_grad_(True)
+            self.optimizer.zero_grad(set_to_none=False)
+            z_vals, dists = self.renderer.sample(rays_o, rays_d, self.model.bound, rays_depth, perturb_rand)
+            ret = self.renderer.eval_points(rays_o, rays_d, z_vals, dists, self.model, None)
+            loss, loss_value = mapping_loss_sharded(ret, rays_color, rays_depth, self.model.compute_sdf_error,
+                                                    None, **self.w)
+            loss.backward()
+            torch.nn.utils.clip_grad_norm_(self.train_params, max_norm=35.0, foreach=True if rays_o.is_cuda else None)
+            self.optimizer.step()
+            d_rays[:, :3], d_rays[:, 3:] = rays_o.grad, rays_d.grad
+            return loss_value, d_rays
+        flat = self.flat
+        flat.check_bindings()
+        args = self._prepare(rays_o, rays_d, rays_color, rays_depth)
+        flat.wait_gather()
+        if n:
+            inv_scale = self._local_gradients(*args, perturb_rand, None, ray_grad_out=d_rays)
+        else:
+            inv_scale = self._local_gradients(*args, perturb_rand, None)
+        flat.step(inv_scale, prepped=True)
+        return self._global_loss(), d_rays
 
     def _global_loss(self):
         """the step's loss over all ranks as a 0-dim tensor (with world > 1 it was summed by the dense all-reduce)"""

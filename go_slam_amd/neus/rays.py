@@ -86,8 +86,12 @@ class RayBank:
         self.big = HW + 1
         self.cums = (cums + self.big * torch.arange(F, device=cums.device)[:, None]).reshape(-1)
 
-    def sample(self, frames, n_rays):
-        """(rays_o, rays_d, color, depth) of `n_rays` random valid pixels of each of `frames`, concatenated in order"""
+    def sample(self, frames, n_rays, camera_frame=False):
+        """(rays_o, rays_d, color, depth) of `n_rays` random valid pixels of each of `frames`, concatenated in order.
+        `camera_frame` (mapping.BA, whose rays are rebuilt from the trained poses in every iteration): the same draw --
+        same generator calls, same pixels -- with the identity pose, i.e. rays_o = 0 and rays_d = the camera-frame
+        directions K^-1 [u, v, 1]; a fifth item then gives the rays per frame (all n_rays, except on the tiny-mask
+        path, which returns every valid pixel of such a frame)."""
         H, W = self.H, self.W
         fx, fy, cx, cy = self.intr
         dev = self.device
@@ -96,14 +100,18 @@ class RayBank:
             parts = [[], [], [], []]                                       # (rare: tiny masks -- the reference's own form)
             for f in frames:
                 color, depth, c2w, _, mask = self.items[f]
+                if camera_frame:
+                    c2w = torch.eye(4, dtype=torch.float32, device=dev)
                 out = build_rays(0, H, 0, W, n_rays, H, W, fx, fy, cx, cy, c2w, depth, color, dev,
                                  nerf_coordinate=False, dir_normalize=False, mask=mask)
                 for acc, x in zip(parts, out):
                     acc.append(x.float())
+            counts = [len(x) for x in parts[0]]
             rays_o, rays_d, depth, color = (torch.cat(p, dim=0) for p in parts)
-            return rays_o, rays_d, color, depth
+            return (rays_o, rays_d, color, depth) + ((counts,) if camera_frame else ())
         if self.fused:
-            return self._sample_fused(pos, n_rays)
+            out = self._sample_fused(pos, n_rays, camera_frame)
+            return out + (([n_rays] * len(pos),) if camera_frame else ())
         # the reference's random draws, call for call
         idx = torch.stack([torch.randint(self.N[p], (n_rays,), device=dev).clamp(0, self.N[p] - 1) for p in pos], 0)
         fi = torch.tensor(pos, dtype=torch.int64, device=dev)
@@ -113,11 +121,15 @@ class RayBank:
         x = (local % W).float()
         y = torch.div(local, W, rounding_mode="floor").float()
         dirs = torch.stack([(x - cx) / fx, (y - cy) / fy, torch.ones_like(x)], dim=-1).reshape(len(pos), n_rays, 3)
+        if camera_frame:
+            out = (torch.zeros(len(pos) * n_rays, 3, dtype=torch.float32, device=dev), dirs.reshape(-1, 3).float(),
+                   self.color[g].float(), self.depth[g].float())
+            return out + ([n_rays] * len(pos),)
         rays_d = torch.bmm(dirs, self.rot_t[fi].to(dirs.dtype)).reshape(-1, 3)
         rays_o = self.trans[fi].to(dirs.dtype)[:, None, :].expand(-1, n_rays, -1).reshape(-1, 3)
         return rays_o.float(), rays_d.float(), self.color[g].float(), self.depth[g].float()
 
-    def _sample_fused(self, pos, n_rays):
+    def _sample_fused(self, pos, n_rays, camera_frame=False):
         """The same draw on the device path: the reference's `torch.randint` calls, call for call (written into the rows of
         one index tensor; `clamp(0, N - 1)` is the identity on their range), then ONE launch (gs_ray_draw: rank -> pixel
         through the running mask sums, directions, origins, colour and depth of every frame's rays)."""
@@ -138,9 +150,16 @@ class RayBank:
         rays_o, rays_d, color = torch.empty(n, 3, **f32), torch.empty(n, 3, **f32), torch.empty(n, 3, **f32)
         depth = torch.empty(n, **f32)
         fx, fy, cx, cy = self.intr
+        rot_t, trans = self.rot_t, self.trans
+        if camera_frame:        # identity poses: d = 1 * [d0, d1, 1] + 0 + 0 exactly, o = 0
+            if getattr(self, "_identity", None) is None:
+                F = rot_t.shape[0]
+                self._identity = (torch.eye(3, dtype=torch.float32, device=dev).expand(F, 3, 3).contiguous(),
+                                  torch.zeros(F, 3, dtype=torch.float32, device=dev))
+            rot_t, trans = self._identity
         with torch.cuda.device(dev):
             rc = _lib.lib().gs_ray_draw(_lib.ptr(idx), _lib.ptr(fpos), _lib.ptr(self.cum32), _lib.ptr(self.color),
-                                        _lib.ptr(self.depth), _lib.ptr(self.rot_t), _lib.ptr(self.trans), nf, n_rays,
+                                        _lib.ptr(self.depth), _lib.ptr(rot_t), _lib.ptr(trans), nf, n_rays,
                                         self.H * self.W, self.W, float(fx), float(fy), float(cx), float(cy),
                                         _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(color), _lib.ptr(depth),
                                         _lib.stream_ptr(dev))

@@ -176,6 +176,23 @@ int gs_neus_backward_points(const float* rays_o, const float* rays_d, const floa
  * arrive as packed atomics).  `bin_ws`: gs_neus_bin_workspace_bytes(n * s) bytes of scratch (no initial state).
  * `sdf_wt` (optional, f32 [16][2][32]): sdf_w's encoding columns transposed, sdf_wt[l][f][o] = sdf_w[o][3 + 2 l + f]
  * (gs_map_step_prep writes it), which turns the kernel's strided weight reads into contiguous ones.                */
+/* Ray gradients of the renderer (mapping.BA; a pass of its own, after gs_neus_backward_points[_binned], with the same
+ * inputs): per sample point dL/dx -- the SDF layer's xyz columns and the hash grid's input gradient, the second-order
+ * path through d sdf / d x (the trilinear interpolation's mixed second derivatives, from the 8 corner values gathered
+ * again), the colour embedding sin(x B) -- and dL/d dir of the NeuS alpha's cos term; then per ray, in a fixed order:
+ * d_rays f32 [n, 6] = [dL/d rays_o | dL/d rays_d] = [sum_k dL/dx_k | sum_k z_mid_k dL/dx_k + dL/d dir_k].
+ * Points outside the realtime bound (mask 0) contribute nothing.  point_ws: f32 [n*s, 6] scratch.                      */
+int gs_neus_backward_raygrad(const float* rays_o, const float* rays_d, const float* z_vals, const float* dists,
+                             const void* grid, const float* sdf_w, const float* color_B, float inv_s,
+                             const float* inv_s_dev, const float* bound_host, const float* sdf, const float* grad,
+                             const uint8_t* mask, const float* d_alpha, const float* d_sdf, const float* d_grad,
+                             const void* dX, int dx_dtype, float dx_scale, const float* d_gerr_ray, float* point_ws,
+                             float* d_rays, int n, int s, gs_stream_t stream);
+/* Camera-pose gradients per visited keyframe entry: rays [seg[e], seg[e+1]) belong to entry e, whose rays were built as
+ * rays_d = dirs @ R^T, rays_o = t.  out f32 [n_entries, 12] = [dL/dR row-major (9) | dL/dt (3)].  One workgroup per
+ * entry, fixed summation order, no atomics (reruns are bitwise identical); segments may be ragged or empty.            */
+int gs_pose_grad_reduce(const float* ray_grad, const float* dirs, const int* seg, int n_entries, float* out,
+                        gs_stream_t stream);
 size_t gs_neus_bin_workspace_bytes(int n_points);
 int gs_neus_backward_points_binned(const float* rays_o, const float* rays_d, const float* z_vals,
                                    const float* dists, const void* grid, const float* sdf_w, const float* color_B,
