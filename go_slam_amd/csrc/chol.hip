@@ -1539,15 +1539,44 @@ __global__ __launch_bounds__(SMALL_NT) void chol_mid_kernel(double* __restrict__
 
 #ifdef CHOL_TIMING
 int g_chol_coop_groups = 128;       // workgroups of the persistent path (all resident at once); tools/chol_bench.hip sweeps it
+extern int g_chol_force_blocked;    // tools/chol_bench.hip: 0 = the product's dispatch, 1 = the multi-kernel path, 2 = the
+                                    // persistent path, whatever n
+extern int g_chol_two_launches;     // tools/chol_bench.hip: the round-5 form of the multi-kernel path
 #endif
 
-int gs_chol_solve_launch(double* H, double* b, int n, float lm, float ep, float* dx_out, int32_t* fail_flag,
-                         int32_t* fail_count, int32_t* sync, hipStream_t st) {
+namespace {
+
+enum { CHOL_PATH_DISPATCH = 0, CHOL_PATH_SMALL = 1, CHOL_PATH_MID = 2, CHOL_PATH_BLOCKED = 3 };
+
+// dynamic LDS of chol_mid_kernel at n (SW = 60 or 30 column stages, then the <= 192-column packed tail)
+size_t chol_mid_lds(int n) {
+  const int SW = n <= MID_SW60_N ? 60 : 30;
+  const size_t tall = (size_t)(n + 1) * (SW + 1);
+  const size_t tail = (size_t)(SMALL_N + 1) * (SMALL_N + 2) / 2 + SMALL_N;
+  return ((size_t)2 * n + (tall > tail ? tall : tail)) * sizeof(double);
+}
+
+bool chol_small_fits(int n) { return n >= 1 && n <= SMALL_N && n % CB == 0; }
+bool chol_mid_fits(int n) {                           // (the kernel also has a few bytes of static LDS)
+  return n >= 1 && n <= MID_N && n % CB == 0 && chol_mid_lds(n) <= 160 * 1024 - 256;
+}
+
+// the product's choice of path for n unknowns
+int chol_dispatch(int n) {
 #ifdef CHOL_TIMING
-  extern int g_chol_force_blocked;                    // tools/chol_bench.hip: 0 = the product's dispatch, 1 = the multi-kernel
-  if (g_chol_force_blocked != 2)                      // path, 2 = the persistent path, whatever n
+  const bool allow_small = g_chol_force_blocked != 2, allow_mid = g_chol_force_blocked == 0;
+#else
+  constexpr bool allow_small = true, allow_mid = true;
 #endif
-  if (n <= SMALL_N && n % CB == 0) {
+  if (allow_small && chol_small_fits(n)) return CHOL_PATH_SMALL;
+  if (allow_mid && chol_mid_fits(n)) return CHOL_PATH_MID;
+  return CHOL_PATH_BLOCKED;
+}
+
+// the three paths; `path` is CHOL_PATH_SMALL / _MID / _BLOCKED and its preconditions hold (chol_small_fits / chol_mid_fits)
+int chol_solve_path(double* H, double* b, int n, float lm, float ep, int path, float* dx_out, int32_t* fail_flag,
+                    int32_t* fail_count, int32_t* sync, hipStream_t st) {
+  if (path == CHOL_PATH_SMALL) {
     const size_t lds = ((size_t)(n + 1) * (n + 2) / 2 + (size_t)n) * sizeof(double);
     static GsLdsLimit limit;
     const size_t cap = ((size_t)(SMALL_N + 1) * (SMALL_N + 2) / 2 + SMALL_N) * sizeof(double);
@@ -1556,24 +1585,16 @@ int gs_chol_solve_launch(double* H, double* b, int n, float lm, float ep, float*
     GS_CHECK_LAUNCH("chol_small");
     return GS_OK;
   }
-#ifdef CHOL_TIMING
-  if (g_chol_force_blocked == 0)
-#endif
-  if (n <= MID_N && n % CB == 0) {                    // the monocular window: one launch, trailing matrix in HBM / L2
+  if (path == CHOL_PATH_MID) {                        // the monocular window: one launch, trailing matrix in HBM / L2
     const int SW = n <= MID_SW60_N ? 60 : 30;
-    const size_t tall = (size_t)(n + 1) * (SW + 1);
-    const size_t tail = (size_t)(SMALL_N + 1) * (SMALL_N + 2) / 2 + SMALL_N;
-    const size_t lds = ((size_t)2 * n + (tall > tail ? tall : tail)) * sizeof(double);
-    if (lds <= 160 * 1024 - 256) {                    // (the kernel also has a few bytes of static LDS)
-      static GsLdsLimit limit;
-      if (int rc = limit.raise((const void*)chol_mid_kernel, lds, "chol_mid")) return rc;
-      chol_mid_kernel<<<1, SMALL_NT, lds, st>>>(H, b, n, (double)lm, (double)ep, SW, dx_out, fail_flag, fail_count);
-      GS_CHECK_LAUNCH("chol_mid");
-      return GS_OK;
-    }
+    const size_t lds = chol_mid_lds(n);
+    static GsLdsLimit limit;
+    if (int rc = limit.raise((const void*)chol_mid_kernel, lds, "chol_mid")) return rc;
+    chol_mid_kernel<<<1, SMALL_NT, lds, st>>>(H, b, n, (double)lm, (double)ep, SW, dx_out, fail_flag, fail_count);
+    GS_CHECK_LAUNCH("chol_mid");
+    return GS_OK;
   }
 #ifdef CHOL_TIMING                                    // (the harness's other forms keep the damping launch)
-  extern int g_chol_two_launches;
   if (g_chol_force_blocked == 2 || g_chol_two_launches) chol_damp_kernel<<<gs_cdiv(n, 256), 256, 0, st>>>(H, n, (double)lm, (double)ep, fail_flag, sync);
 #endif
 #ifdef CHOL_TIMING
@@ -1631,4 +1652,29 @@ int gs_chol_solve_launch(double* H, double* b, int n, float lm, float ep, float*
     GS_CHECK_LAUNCH("chol_back_block");
   }
   return GS_OK;
+}
+
+}  // namespace
+
+int gs_chol_solve_launch(double* H, double* b, int n, float lm, float ep, float* dx_out, int32_t* fail_flag,
+                         int32_t* fail_count, int32_t* sync, hipStream_t st) {
+  return chol_solve_path(H, b, n, lm, ep, chol_dispatch(n), dx_out, fail_flag, fail_count, sync, st);
+}
+
+extern "C" int gs_chol_solve(double* H, double* b, int n, float lm, float ep, int path, float* dx, int32_t* status,
+                             gs_stream_t stream) {
+  GS_REQUIRE(n >= 1, "chol_solve: n = %d < 1", n);
+  GS_REQUIRE(path >= CHOL_PATH_DISPATCH && path <= CHOL_PATH_BLOCKED, "chol_solve: unknown path %d (0 .. 3)", path);
+  if (path == CHOL_PATH_SMALL && !chol_small_fits(n)) {
+    gs_set_error("chol_solve: the small path needs n <= %d and n %% %d == 0 (n = %d)", SMALL_N, CB, n);
+    return GS_ERR_UNSUPPORTED;
+  }
+  if (path == CHOL_PATH_MID && !chol_mid_fits(n)) {
+    gs_set_error("chol_solve: the mid path needs n <= %d, n %% %d == 0 and %zu B of LDS to fit (n = %d)", MID_N, CB,
+                 chol_mid_lds(n), n);
+    return GS_ERR_UNSUPPORTED;
+  }
+  GS_REQUIRE(H && b && dx && status, "chol_solve: null pointer");
+  if (path == CHOL_PATH_DISPATCH) path = chol_dispatch(n);
+  return chol_solve_path(H, b, n, lm, ep, path, dx, status, status + 1, status + 2, (hipStream_t)stream);
 }

@@ -402,6 +402,19 @@ int gs_ba_ex(float* poses, float* disps, const float* intrinsics, const float* d
              float* dx, float* dz, int32_t* status_out,
              void* workspace, size_t workspace_bytes, int flags, gs_stream_t stream);
 
+/* The damped fp64 Cholesky solve of gs_ba's reduced camera system on its own (Eigen SimplicialLLT, droid_kernels.cu:
+ * 1192-1213): x = (A + diag(ep + lm * diag(A)))^-1 b, dx = float(x); a pivot <= 0 gives dx = 0 (a NaN pivot does not).
+ *   H f64 [n,n] row-major, only its LOWER triangle is read; b f64 [n].  Both are device buffers and both may be
+ *     overwritten (the mid and blocked paths work in place; the blocked path leaves L in H's lower triangle and uses
+ *     b for y = L^-1 b and the backward substitution's partial sums); dx f32 [n].
+ *   path: 0 = gs_ba's own choice by n, 1 = the one-workgroup LDS path (n <= 192, n % 6 == 0), 2 = the one-workgroup
+ *     path with global head stages (n % 6 == 0, n <= 300), 3 = the blocked multi-launch path (any n >= 1).  A forced
+ *     path whose limits n does not meet is refused with GS_ERR_UNSUPPORTED before anything is enqueued.
+ *   status: device int32[4]; [0] = 1 if this solve failed, else 0; [1] += 1 per failed solve; [2..3] scratch of the
+ *     solver (gs_ba's own header words).                                                                           */
+int gs_chol_solve(double* H, double* b, int n, float lm, float ep, int path, float* dx, int32_t* status,
+                  gs_stream_t stream);
+
 /* Edge proposal with greedy non-maximum suppression on the device: FactorGraph.add_proximity_factors
  * (src/factor_graph.py:384-450) and Backend.ba's selection incl. the loop-closure rule (src/backend.py:31-94), in two
  * launches around a device-side stable sort; the frame-distance matrix never leaves HBM.
