@@ -113,10 +113,8 @@ __global__ __launch_bounds__(256) void render_sample_kernel(
   dd[total - 1] = span / (float)ns;    // mean over identical columns of (far-near)/N_samples (:149)
 }
 
-// Wave-per-ray variant (n_samples, n_surface <= 64): lane j owns stratified sample j and
-// near-surface sample j; the merge position of each is its index plus its rank in the other run
-// (ties resolved like the sequential merge: stratified first), so every lane writes its own
-// slot and all global traffic is coalesced.  Values are bit-identical to the sequential kernel.
+// Wave-per-ray variant (n_samples, n_surface <= 64; the placement itself is gs_place_ray_wave, neus_common.h): every
+// lane writes its own slot and all global traffic is coalesced.  Values are bit-identical to the sequential kernel.
 __global__ __launch_bounds__(256) void render_sample_wave_kernel(
     const float* __restrict__ rays_o, const float* __restrict__ rays_d, const float* __restrict__ gt_depth,
     const float* __restrict__ bound, const float* __restrict__ t_samples, const float* __restrict__ t_surface,
@@ -156,73 +154,12 @@ __global__ __launch_bounds__(256) void render_sample_wave_kernel(
   }
   const int r = blockIdx.x * 4 + wave;
   if (r >= n) return;
-  float far_bb = INFINITY;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float o = rays_o[r * 3 + k], d = rays_d[r * 3 + k];
-    const float t0 = (bound[2 * k + 0] - o) / d;
-    const float t1 = (bound[2 * k + 1] - o) / d;
-    const float tm = (t0 != t0 || t1 != t1) ? NAN : fmaxf(t0, t1);
-    far_bb = (tm != tm || far_bb != far_bb) ? NAN : fminf(far_bb, tm);
-  }
-  far_bb = far_bb + 0.01f;
+  const float o[3] = {rays_o[r * 3 + 0], rays_o[r * 3 + 1], rays_o[r * 3 + 2]};
+  const float d[3] = {rays_d[r * 3 + 0], rays_d[r * 3 + 1], rays_d[r * 3 + 2]};
   const bool has_depth = gt_depth != nullptr;
-  const float gd = has_depth ? gt_depth[r] : 0.0f;
-  float nearv, farv;
-  if (has_depth) {
-    nearv = gd * 0.01f;
-    farv = fminf(fmaxf(far_bb, 0.0f), gt_max * 1.2f);
-    if (far_bb != far_bb) farv = far_bb;
-  } else {
-    nearv = 0.01f;
-    farv = far_bb;
-    nsurf = 0;
-  }
-  const int total = ns + nsurf;
-  const float span = farv - nearv;
-  auto zu = [&](int j) { return nearv + span * t_samples[j]; };
-  // (descending runs -- far < near, or no-depth rays under a batch maximum below 0.001 -- are walked backwards: the
-  // merge below then equals the reference's sort in those degenerate cases too; without near-surface samples the
-  // reference does not sort, render.py:162, and the run is left as it is)
-  const bool rev_a = span < 0.0f && nsurf > 0, rev_b = !(gd > 0.0f) && gt_max < 0.001f;
-  float za = INFINITY, zb = INFINITY;
-  if (lane < ns) {
-    const int j = rev_a ? ns - 1 - lane : lane;
-    float z = zu(j);
-    if (perturb) {
-      const float lo = (j == 0) ? z : 0.5f * (zu(j - 1) + z);
-      const float hi = (j == ns - 1) ? z : 0.5f * (z + zu(j + 1));
-      z = lo + (hi - lo) * perturb[j];
-    }
-    za = z;
-  }
-  if (lane < nsurf) {
-    const float t = t_surface[rev_b ? nsurf - 1 - lane : lane];
-    if (gd > 0.0f) {
-      const float snr = (1.0f - 0.1f) * gd, sfar = (1.0f + 0.1f) * gd;
-      zb = (snr + (sfar - snr) * t) * 1.0f + (0.001f + (gt_max - 0.001f) * t) * (1.0f - 1.0f);
-    } else {
-      const float vd = gd * 0.0f;
-      const float snr = (1.0f - 0.1f) * vd, sfar = (1.0f + 0.1f) * vd;
-      zb = (snr + (sfar - snr) * t) * 0.0f + (0.001f + (gt_max - 0.001f) * t) * (1.0f - 0.0f);
-    }
-  }
-  sa[wave][lane] = za;
-  sb[wave][lane] = zb;
-  __syncthreads();
-  int ra = 0, rb = 0;      // #surface < za ; #stratified <= zb
-  for (int k = 0; k < nsurf; ++k) ra += (sb[wave][k] < za) ? 1 : 0;
-  for (int k = 0; k < ns; ++k) rb += (sa[wave][k] <= zb) ? 1 : 0;
-  if (lane < ns) sz[wave][lane + ra] = za;
-  if (lane < nsurf) sz[wave][lane + rb] = zb;
-  __syncthreads();
-  float* zo = z_vals + (size_t)r * total;
-  float* dd = dists + (size_t)r * total;
-  for (int k = lane; k < total; k += 64) {
-    const float z = sz[wave][k];
-    zo[k] = z;
-    dd[k] = (k + 1 < total) ? sz[wave][k + 1] - z : span / (float)ns;
-  }
+  const int total = ns + (has_depth ? nsurf : 0);
+  gs_place_ray_wave(o, d, bound, has_depth, has_depth ? gt_depth[r] : 0.0f, gt_max, t_samples, t_surface, perturb, ns,
+                    nsurf, sa[wave], sb[wave], sz[wave], z_vals + (size_t)r * total, dists + (size_t)r * total, lane);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -455,6 +392,7 @@ struct NeusArgs {
   const float* rt_bound_dev;               // != nullptr: the realtime bound lives in device memory (replayed graphs see
                                            // InstantNeuS.update_bound without a re-capture)
   int n, s;
+  int seg_batch, seg_piece;                // pieces (gs_piece_range): runs of seg_piece rays inside batches of seg_batch
 };
 
 __device__ __forceinline__ bool point_of(const NeusArgs& A, int idx, float pt[3], float dir[3], float& zm, float& dist) {
@@ -549,9 +487,11 @@ __global__ __launch_bounds__(256) void neus_encode_levels_kernel(NeusArgs A, gs_
 // and past-the-end lanes contribute zero rows.
 // `flags` (one byte per wave, every one written by the main pass -- nothing to zero beforehand): whether ANY of the wave's
 // points lies in the realtime bound; the reference forces the first 100 points valid when none does
-// (InstantNeuS.py:311-312), which a second launch of this kernel with force_pass = 1 and ONE workgroup handles: it ORs
-// the flags and returns at once unless all are 0 (a 3 us launch instead of the full-size neus_count_kernel pass over
-// all points that used to precede the main pass).
+// (InstantNeuS.py:311-312), which a second launch of this kernel with force_pass = 1 and ONE workgroup PER PIECE handles
+// (a piece: the run of rays one reference forward call would see, gs_piece_range): it ORs the flags of the waves inside
+// the piece, tests the piece's points in the (at most two) waves it shares with its neighbours itself, and returns at
+// once unless none is in bound (a 3 us launch instead of the full-size neus_count_kernel pass over all points that used
+// to precede the main pass).
 // 4 waves per SIMD (amdgpu_waves_per_eu): 124 VGPRs without scratch, 4 x 40 KB workgroups = a CU's LDS exactly.  Left to
 // itself the compiler takes 188 VGPRs (2 waves per SIMD, more gathers in flight per wave) -- measured on one box: 156 vs
 // 130 us for the 4096-ray batch (4608 waves: 2.25 rounds of 2048 resident waves vs 1.125 of 4096), render 19.4 -> 22.1
@@ -566,37 +506,52 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   // consecutive samples of a ray share most cells).  rec == nullptr (the one-workgroup force pass, whose points were out of
   // bound and have no records): every level is gathered here.
   __shared__ __attribute__((aligned(16))) _Float16 xs_all[4 * 64 * XS];
-  const int idx = blockIdx.x * 256 + threadIdx.x;
   const int np = A.n * A.s;
-  const bool valid = idx < np;
+  // the force pass runs one 128-thread workgroup per piece over the piece's first 128 points [p0, min(p0 + 128, p1))
+  int p0 = 0, p1 = np;
+  if (force_pass) {
+    int r0, r1;
+    gs_piece_range(blockIdx.x, A.n, A.seg_batch, A.seg_piece, r0, r1);
+    p0 = r0 * A.s;
+    p1 = r1 * A.s;
+  }
+  const int idx = force_pass ? p0 + (int)threadIdx.x : blockIdx.x * 256 + threadIdx.x;
+  const bool valid = idx < p1;
   const int lane = threadIdx.x & 63;
   _Float16* xs = xs_all + (threadIdx.x >> 6) * 64 * XS;
   half8* xrow = reinterpret_cast<half8*>(xs + lane * XS);
   float pt[3], dir[3], zm = 0.f, dist = 0.f;
   bool in = false;
-  if (force_pass) {                                 // one workgroup: did any wave of the main pass see a point in bound?
-    const int nw = (np + 63) >> 6;
-    int any = 0;                                    // (every wave scans all flags itself: no LDS, no barrier)
-    for (int i0 = lane * 16; i0 < nw; i0 += 8 * 1024) {    // eight 16-byte loads in flight (36 dependent trips at 32768
-      uint4 v[8];                                          // rays otherwise: 20 us for a pass that has nothing to do)
+  if (force_pass) {                                 // one workgroup per piece: did any point of the piece lie in bound?
+    const int nw_end = p1 >> 6;                     // waves wholly inside [p0, p1): their flags; the (at most two) partial
+    const int nw_beg = (p0 + 63) >> 6;              // waves at the piece's ends: their points of the piece tested here
+    int any = 0;                                    // (every wave scans for itself: no LDS, no barrier)
+    for (int i0 = (nw_beg & ~15) + lane * 16; i0 < nw_end; i0 += 8 * 1024) {    // eight 16-byte loads in flight (36
+      uint4 v[8];                                                              // dependent trips at 32768 rays otherwise)
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         const int i = i0 + 1024 * u;
-        v[u] = i + 16 <= nw ? *reinterpret_cast<const uint4*>(flags + i) : make_uint4(0u, 0u, 0u, 0u);
+        v[u] = (i >= nw_beg && i + 16 <= nw_end) ? *reinterpret_cast<const uint4*>(flags + i) : make_uint4(0u, 0u, 0u, 0u);
       }
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         const int i = i0 + 1024 * u;
         any |= (v[u].x | v[u].y | v[u].z | v[u].w) != 0u;
-        if (i < nw && i + 16 > nw)
-          for (int k = i; k < nw; ++k) any |= flags[k];
+        if (i < nw_end && i + 16 > nw_beg && !(i >= nw_beg && i + 16 <= nw_end))
+          for (int k = i > nw_beg ? i : nw_beg; k < nw_end && k < i + 16; ++k) any |= flags[k];
       }
+    }
+    {
+      float q[3], qd[3], qz, qs;
+      const int ha = p0 + lane, hb = (nw_end << 6 > p0 ? nw_end << 6 : p0) + lane;
+      if (ha < p1 && ha < (nw_beg << 6)) any |= point_of(A, ha, q, qd, qz, qs) ? 1 : 0;
+      if (hb < p1) any |= point_of(A, hb, q, qd, qz, qs) ? 1 : 0;
     }
     if (__ballot(any != 0) != 0ull) return;         // (uniform) some point was in bound: nothing to force
   }
   if (valid) {
     in = point_of(A, idx, pt, dir, zm, dist);
-    if (force_pass && idx < 100) in = true;         // InstantNeuS.py:311-312
+    if (force_pass && idx - p0 < 100) in = true;    // InstantNeuS.py:311-312, per piece
     zmid_out[idx] = zm;
     mask_out[idx] = in ? 1 : 0;
   }
@@ -729,12 +684,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   wave_lds_sync();
   float16v co[2];
   wave_mlp64(xs, mlp_w, lane, co);
-  const int wave_p0 = blockIdx.x * 256 + (threadIdx.x >> 6) * 64;
+  const int wave_p0 = (force_pass ? p0 : blockIdx.x * 256) + (threadIdx.x >> 6) * 64;
 #pragma unroll
   for (int nt = 0; nt < 2; ++nt) {
     const int on = __shfl((int)in, (32 * nt + lane) & 63, 64);
     const int pnt = wave_p0 + 32 * nt + lane;
-    if (lane < 32 && pnt < np) {
+    if (lane < 32 && pnt < p1) {
 #pragma unroll
       for (int o = 0; o < 3; ++o) {
         float v = (float)(_Float16)co[nt][o];      // network output is fp16
@@ -887,7 +842,7 @@ __global__ __launch_bounds__(256) void neus_ray_kernel(const float* __restrict__
                                                        float* __restrict__ normal, float* __restrict__ weight_sum,
                                                        float* __restrict__ gerr, float gerr_scale,
                                                        float* __restrict__ sdf_var_out, float sdf_var_value,
-                                                       int n, int s) {
+                                                       int n, int s, int seg_batch, int seg_piece, int piece_mean) {
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= n) return;
@@ -947,9 +902,34 @@ __global__ __launch_bounds__(256) void neus_ray_kernel(const float* __restrict__
     depth[r] = dep;
     depth_var[r] = var;
     weight_sum[r] = wsum;
+    if (piece_mean) {       // 1 / (n_piece s) of the ray's piece, rounded from double as the host's own scale is
+      int r0, r1;
+      const int b = r / seg_batch;
+      gs_piece_range(b * ((seg_batch + seg_piece - 1) / seg_piece) + (r - b * seg_batch) / seg_piece, n, seg_batch,
+                     seg_piece, r0, r1);
+      gerr_scale = (float)(1.0 / (double)((long long)(r1 - r0) * s));
+    }
     gerr[r] = ge * gerr_scale;
     if (sdf_var_out) sdf_var_out[r] = sdf_var_value;
   }
+}
+
+// Per piece: the sum of its rays' scaled eikonal terms (= the piece's `gradient_error`, InstantNeuS.py:360-362) in fp64,
+// in a fixed order (no atomics: the same bits on every run).
+__global__ __launch_bounds__(256) void neus_piece_sum_kernel(const float* __restrict__ gerr, float* __restrict__ out,
+                                                             int n, int seg_batch, int seg_piece) {
+  __shared__ double part[256];
+  int r0, r1;
+  gs_piece_range(blockIdx.x, n, seg_batch, seg_piece, r0, r1);
+  double acc = 0.0;
+  for (int r = r0 + (int)threadIdx.x; r < r1; r += 256) acc += (double)gerr[r];
+  part[threadIdx.x] = acc;
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) part[threadIdx.x] += part[threadIdx.x + h];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[blockIdx.x] = (float)part[0];
 }
 
 gs_grid_meta host_meta() {
@@ -1093,21 +1073,21 @@ extern "C" size_t gs_neus_forward_workspace_bytes(int n, int s) {
   return carve_neus(nullptr, n, s, lm ? hashed_levels(host_meta(), nullptr) : 0).total + 256;
 }
 
-extern "C" int gs_neus_forward(const float* rays_o, const float* rays_d, const float* z_vals, const float* dists,
-                               const void* grid, const float* sdf_w, const float* sdf_b, const float* color_B,
-                               const void* mlp, float inv_s, const float* inv_s_dev, const float* bound_host,
-                               const float* rt_bound_host, const float* rt_bound_dev,
-                               float* color, float* depth, float* depth_var, float* normal, float* weight_sum,
-                               float* sdf, float* z_mid, float* grad_err_ray, float* alpha_out, void* rgb_out,
-                               float* grad_out, uint8_t* mask_out, void* mlp_in_out, void* enc_aux_out, float grad_err_scale,
-                               float* sdf_variance_out, float sdf_variance_value, int n, int s,
-                               void* workspace, size_t workspace_bytes, gs_stream_t stream) {
+extern "C" int gs_neus_forward_segmented(
+    const float* rays_o, const float* rays_d, const float* z_vals, const float* dists, const void* grid,
+    const float* sdf_w, const float* sdf_b, const float* color_B, const void* mlp, float inv_s, const float* inv_s_dev,
+    const float* bound_host, const float* rt_bound_host, const float* rt_bound_dev, float* color, float* depth,
+    float* depth_var, float* normal, float* weight_sum, float* sdf, float* z_mid, float* grad_err_ray, float* alpha_out,
+    void* rgb_out, float* grad_out, uint8_t* mask_out, void* mlp_in_out, void* enc_aux_out, float grad_err_scale,
+    int piece_mean, float* grad_err_piece, float* sdf_variance_out, float sdf_variance_value, int n, int s,
+    int ray_batch, int piece_rays, void* workspace, size_t workspace_bytes, gs_stream_t stream) {
   GS_REQUIRE(rays_o && rays_d && z_vals && dists && grid && sdf_w && sdf_b && color_B && mlp && bound_host &&
                  rt_bound_host, "neus_forward: null input");
   GS_REQUIRE(color && depth && depth_var && normal && weight_sum && sdf && z_mid && grad_err_ray,
              "neus_forward: null output");
-  GS_REQUIRE(n >= 0 && s > 0, "neus_forward: bad shape");
+  GS_REQUIRE(n >= 0 && s > 0 && ray_batch > 0 && piece_rays > 0, "neus_forward: bad shape");
   if (n == 0) return GS_OK;
+  const int n_pieces = gs_piece_count(n, ray_batch, piece_rays);
   const gs_grid_meta meta = host_meta();
   int first_hashed = GS_GRID_LEVELS;
   int nh = hashed_levels(meta, &first_hashed);
@@ -1135,6 +1115,7 @@ extern "C" int gs_neus_forward(const float* rays_o, const float* rays_d, const f
   for (int k = 0; k < 6; ++k) { A.bound[k] = bound_host[k]; A.rt_bound[k] = rt_bound_host[k]; }
   A.rt_bound_dev = rt_bound_dev;
   A.n = n; A.s = s;
+  A.seg_batch = ray_batch; A.seg_piece = piece_rays;
   const int np = n * s;
   float* alpha = alpha_out ? alpha_out : ws.alpha;
   float* grad = grad_out ? grad_out : ws.grad;
@@ -1153,13 +1134,39 @@ extern "C" int gs_neus_forward(const float* rays_o, const float* rays_d, const f
                                                       (_Float16*)mlp_in_out, (_Float16*)enc_aux_out, (const _Float16*)mlp,
                                                       rgb, nh > 0 ? ws.rec : nullptr, first_hashed);
   GS_CHECK_LAUNCH("neus_point");
-  neus_point_kernel<<<1, 128, 0, st>>>(A, meta, ws.flags, 1, sdf, z_mid, alpha, grad, ws.mask,   // points 0..127
+  neus_point_kernel<<<n_pieces, 128, 0, st>>>(A, meta, ws.flags, 1, sdf, z_mid, alpha, grad, ws.mask,  // 128 per piece
                                        (_Float16*)mlp_in_out, (_Float16*)enc_aux_out, (const _Float16*)mlp, rgb, nullptr,
                                        first_hashed);
   GS_CHECK_LAUNCH("neus_force100");
   neus_ray_kernel<<<gs_cdiv(n, 4), 256, 0, st>>>(alpha, rgb, z_mid, grad, ws.mask, color, depth, depth_var, normal,
                                                    weight_sum, grad_err_ray, grad_err_scale, sdf_variance_out,
-                                                   sdf_variance_value, n, s);
+                                                   sdf_variance_value, n, s, ray_batch, piece_rays, piece_mean);
   GS_CHECK_LAUNCH("neus_ray");
+  if (grad_err_piece) {
+    neus_piece_sum_kernel<<<n_pieces, 256, 0, st>>>(grad_err_ray, grad_err_piece, n, ray_batch, piece_rays);
+    GS_CHECK_LAUNCH("neus_piece_sum");
+  }
   return GS_OK;
+}
+
+extern "C" int gs_neus_forward_pieces(int n, int ray_batch, int piece_rays) {
+  if (n < 0 || ray_batch <= 0 || piece_rays <= 0) return 0;
+  return gs_piece_count(n, ray_batch, piece_rays);
+}
+
+extern "C" int gs_neus_forward(const float* rays_o, const float* rays_d, const float* z_vals, const float* dists,
+                               const void* grid, const float* sdf_w, const float* sdf_b, const float* color_B,
+                               const void* mlp, float inv_s, const float* inv_s_dev, const float* bound_host,
+                               const float* rt_bound_host, const float* rt_bound_dev,
+                               float* color, float* depth, float* depth_var, float* normal, float* weight_sum,
+                               float* sdf, float* z_mid, float* grad_err_ray, float* alpha_out, void* rgb_out,
+                               float* grad_out, uint8_t* mask_out, void* mlp_in_out, void* enc_aux_out, float grad_err_scale,
+                               float* sdf_variance_out, float sdf_variance_value, int n, int s,
+                               void* workspace, size_t workspace_bytes, gs_stream_t stream) {
+  // one piece: the whole call
+  return gs_neus_forward_segmented(rays_o, rays_d, z_vals, dists, grid, sdf_w, sdf_b, color_B, mlp, inv_s, inv_s_dev,
+                                   bound_host, rt_bound_host, rt_bound_dev, color, depth, depth_var, normal, weight_sum,
+                                   sdf, z_mid, grad_err_ray, alpha_out, rgb_out, grad_out, mask_out, mlp_in_out,
+                                   enc_aux_out, grad_err_scale, 0, nullptr, sdf_variance_out, sdf_variance_value, n, s,
+                                   n > 0 ? n : 1, n > 0 ? n : 1, workspace, workspace_bytes, stream);
 }

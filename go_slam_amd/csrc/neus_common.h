@@ -1,5 +1,5 @@
-// Hash-grid helpers shared by the NeuS kernels (neus.hip, neus_bwd.hip, grid_autograd.hip): tiny-cuda-nn HashGrid
-// indexing and the wave-merged table-gradient scatter.
+// Helpers shared by the NeuS kernels (neus.hip, neus_bwd.hip, grid_autograd.hip, render_img.hip): tiny-cuda-nn HashGrid
+// indexing, the wave-merged table-gradient scatter, the per-ray sample placement and the piece layout of a segmented call.
 #pragma once
 #include "common.h"
 #include "../../include/goslam_neus.h"
@@ -171,6 +171,101 @@ __device__ __forceinline__ void lvl_scatter(float* __restrict__ tab, _Float16* _
       if (gacc[c][1] != 0.0f) atomicAdd(gp + 1, gacc[c][1]);
     }
   }
+}
+
+// ---------------------------------------------------------------------------------------
+// Sample placement of ONE ray by one wave (Renderer.render_batch_ray, src/render.py:99-171): ray/AABB far bound,
+// stratified + near-surface samples, the merge of the two sorted runs (= the reference's torch.sort), dists.  Shared by
+// gs_render_sample's wave kernel (one batch) and the whole-image sampler of render_img.hip (many batches), so that both
+// place bit-identical samples from the same ray, batch maximum and perturbation row.  n_samples, n_surface <= 64: lane j
+// owns stratified sample j and near-surface sample j; the merge position of each is its index plus its rank in the other
+// run (ties resolved like the sequential merge: stratified first).  `sa`, `sb`, `sz`: the wave's own LDS rows (64, 64,
+// 128 floats).  Every wave of the workgroup that has a ray must call this (it holds two workgroup barriers).
+__device__ __forceinline__ void gs_place_ray_wave(const float o[3], const float d[3], const float* __restrict__ bound,
+                                                  bool has_depth, float gd, float gt_max,
+                                                  const float* __restrict__ t_samples, const float* __restrict__ t_surface,
+                                                  const float* __restrict__ perturb, int ns, int nsurf,
+                                                  float* sa, float* sb, float* sz,
+                                                  float* __restrict__ zo, float* __restrict__ dd, int lane) {
+  // far_bb = min_dim max((b0-o)/d, (b1-o)/d) + 0.01        (render.py:112-118; torch.max / torch.min propagate NaN)
+  float far_bb = INFINITY;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float t0 = (bound[2 * k + 0] - o[k]) / d[k];
+    const float t1 = (bound[2 * k + 1] - o[k]) / d[k];
+    const float tm = (t0 != t0 || t1 != t1) ? NAN : fmaxf(t0, t1);
+    far_bb = (tm != tm || far_bb != far_bb) ? NAN : fminf(far_bb, tm);
+  }
+  far_bb = far_bb + 0.01f;
+  float nearv, farv;
+  if (has_depth) {
+    nearv = gd * 0.01f;
+    farv = fminf(fmaxf(far_bb, 0.0f), gt_max * 1.2f);     // torch.clamp(far_bb, 0, max)
+    if (far_bb != far_bb) farv = far_bb;
+  } else {
+    nearv = 0.01f;
+    farv = far_bb;
+    nsurf = 0;
+  }
+  const int total = ns + nsurf;
+  const float span = farv - nearv;
+  auto zu = [&](int j) { return nearv + span * t_samples[j]; };
+  // (descending runs -- far < near, or no-depth rays under a batch maximum below 0.001 -- are walked backwards: the
+  // merge below then equals the reference's sort in those degenerate cases too; without near-surface samples the
+  // reference does not sort, render.py:162, and the run is left as it is)
+  const bool rev_a = span < 0.0f && nsurf > 0, rev_b = !(gd > 0.0f) && gt_max < 0.001f;
+  float za = INFINITY, zb = INFINITY;
+  if (lane < ns) {
+    const int j = rev_a ? ns - 1 - lane : lane;
+    float z = zu(j);
+    if (perturb) {
+      const float lo = (j == 0) ? z : 0.5f * (zu(j - 1) + z);
+      const float hi = (j == ns - 1) ? z : 0.5f * (z + zu(j + 1));
+      z = lo + (hi - lo) * perturb[j];
+    }
+    za = z;
+  }
+  if (lane < nsurf) {
+    const float t = t_surface[rev_b ? nsurf - 1 - lane : lane];
+    if (gd > 0.0f) {
+      const float snr = (1.0f - 0.1f) * gd, sfar = (1.0f + 0.1f) * gd;
+      zb = (snr + (sfar - snr) * t) * 1.0f + (0.001f + (gt_max - 0.001f) * t) * (1.0f - 1.0f);
+    } else {
+      const float vd = gd * 0.0f;
+      const float snr = (1.0f - 0.1f) * vd, sfar = (1.0f + 0.1f) * vd;
+      zb = (snr + (sfar - snr) * t) * 0.0f + (0.001f + (gt_max - 0.001f) * t) * (1.0f - 0.0f);
+    }
+  }
+  sa[lane] = za;
+  sb[lane] = zb;
+  __syncthreads();
+  int ra = 0, rb = 0;      // #surface < za ; #stratified <= zb
+  for (int k = 0; k < nsurf; ++k) ra += (sb[k] < za) ? 1 : 0;
+  for (int k = 0; k < ns; ++k) rb += (sa[k] <= zb) ? 1 : 0;
+  if (lane < ns) sz[lane + ra] = za;
+  if (lane < nsurf) sz[lane + rb] = zb;
+  __syncthreads();
+  for (int k = lane; k < total; k += 64) {
+    const float z = sz[k];
+    zo[k] = z;
+    dd[k] = (k + 1 < total) ? sz[k + 1] - z : span / (float)ns;    // last: mean of (far-near)/N_samples (:149)
+  }
+}
+
+// Piece k of a call that covers n rays in ray batches of `batch` rays, each cut into runs of `piece` rays (the last
+// batch and the last piece of a batch ragged): rays [r0, r1).  Batches hold ceil(batch / piece) pieces each, in order.
+__device__ __host__ __forceinline__ void gs_piece_range(int k, int n, int batch, int piece, int& r0, int& r1) {
+  const int ppb = (batch + piece - 1) / piece;
+  const int b = k / ppb, j = k - b * ppb;
+  const int bend = b * batch + batch < n ? b * batch + batch : n;
+  r0 = b * batch + j * piece;
+  r1 = r0 + piece < bend ? r0 + piece : bend;
+}
+__device__ __host__ __forceinline__ int gs_piece_count(int n, int batch, int piece) {
+  if (n <= 0) return 0;
+  const int nb = (n + batch - 1) / batch, ppb = (batch + piece - 1) / piece;
+  const int last = n - (nb - 1) * batch;
+  return (nb - 1) * ppb + (last + piece - 1) / piece;
 }
 
 }  // namespace

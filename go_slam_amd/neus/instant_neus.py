@@ -410,6 +410,38 @@ def _neus_forward_raw(model, rays_o, rays_d, z_vals, dists, inv_s, save, inv_s_d
     return color, depth, dvar, normal, wsum, sdf, gerr, zmid, saved
 
 
+def _neus_forward_segmented_raw(model, rays_o, rays_d, z_vals, dists, ray_batch, piece_rays, out):
+    """No-gradient forward of many reference forward calls at once (gs_neus_forward_segmented): the rays are cut into
+    ray batches of `ray_batch` rays and those into pieces of `piece_rays` rays, and every piece behaves as one
+    `InstantNeuS.forward` call on its rays (the in-bound fallback of InstantNeuS.py:311-312 and the `gradient_error` mean
+    are per piece).  `out`: preallocated outputs (views into image-sized buffers are fine) -- color, normal [n,3];
+    depth, depth_variance, weight_sum, sdf_variance [n,1]; sdf, z_vals [n,s]; gerr_ray [n] (scratch);
+    gradient_error [#pieces]."""
+    net = model.sdf_network
+    dev = rays_o.device
+    n, s = z_vals.shape
+    var, inv_s = model._inv_s()
+    bh, rh = model._bounds_host()
+    L = _lib.lib()
+    ws = _workspace(dev, L.gs_neus_forward_workspace_bytes(n, s) + 256)
+    grid = net.encoding.encoding.params_half()
+    mlp = model.color_network.network.params_half()
+    sdf_w = net.sdf_layer.weight.detach().float().contiguous()
+    sdf_b = net.sdf_layer.bias.detach().float().contiguous()
+    cB = model.color_network._B.detach().float().contiguous()
+    o = out
+    with torch.cuda.device(dev):
+        rc = L.gs_neus_forward_segmented(
+            _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(z_vals), _lib.ptr(dists), _lib.ptr(grid), _lib.ptr(sdf_w),
+            _lib.ptr(sdf_b), _lib.ptr(cB), _lib.ptr(mlp), float(inv_s), None, bh, rh, None,
+            _lib.ptr(o["color"]), _lib.ptr(o["depth"]), _lib.ptr(o["depth_variance"]), _lib.ptr(o["normal"]),
+            _lib.ptr(o["weight_sum"]), _lib.ptr(o["sdf"]), _lib.ptr(o["z_vals"]), _lib.ptr(o["gerr_ray"]),
+            None, None, None, None, None, None, 1.0, 1, _lib.ptr(o["gradient_error"]), _lib.ptr(o["sdf_variance"]),
+            float(1.0 / math.exp(var * model.variance_network.scale_factor)), n, s, int(ray_batch), int(piece_rays),
+            _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+    _lib.check(rc, "InstantNeuS segmented forward")
+
+
 _BIN_WS = {}
 
 

@@ -113,6 +113,57 @@ int gs_neus_forward(const float* rays_o, const float* rays_d, const float* z_val
                     float sdf_variance_value, int n, int s,
                     void* workspace, size_t workspace_bytes, gs_stream_t stream);
 
+/* gs_neus_forward over MANY reference forward calls at once: the n rays are cut into ray batches of `ray_batch` rays and
+ * each batch into pieces of `piece_rays` rays (the last batch and the last piece of every batch ragged; piece k of
+ * batch b follows all pieces of batch b - 1) -- the calls Renderer.eval_points makes inside Renderer.render_img
+ * (src/render.py:29-71,216-233).  Per piece, as one gs_neus_forward call on its rays would: the first 100 points are
+ * forced valid when none of the piece lies in the realtime bound (InstantNeuS.py:311-312), and with piece_mean != 0
+ * grad_err_ray[r] is pre-scaled by 1 / (n_piece s) of its own piece (grad_err_scale is then ignored), so that
+ * grad_err_piece f32 [gs_neus_forward_pieces(n, ray_batch, piece_rays)] (optional) -- the per-piece sums of grad_err_ray
+ * in fp64, in a fixed order -- is the `gradient_error` of every call, in order.  The other arguments and outputs are
+ * gs_neus_forward's; gs_neus_forward is this call with one piece (ray_batch = piece_rays = n, piece_mean = 0).
+ * The workspace is gs_neus_forward_workspace_bytes(n, s).                                                          */
+int gs_neus_forward_pieces(int n, int ray_batch, int piece_rays);
+int gs_neus_forward_segmented(const float* rays_o, const float* rays_d, const float* z_vals,
+                              const float* dists, const void* grid, const float* sdf_w, const float* sdf_b,
+                              const float* color_B, const void* mlp, float inv_s, const float* inv_s_dev,
+                              const float* bound_host, const float* rt_bound_host, const float* rt_bound_dev,
+                              float* color, float* depth, float* depth_var, float* normal,
+                              float* weight_sum, float* sdf, float* z_mid, float* grad_err_ray,
+                              float* alpha_out, void* rgb_out, float* grad_out, uint8_t* mask_out,
+                              void* mlp_in_out, void* enc_aux_out, float grad_err_scale, int piece_mean,
+                              float* grad_err_piece, float* sdf_variance_out, float sdf_variance_value, int n, int s,
+                              int ray_batch, int piece_rays, void* workspace, size_t workspace_bytes,
+                              gs_stream_t stream);
+
+/* Renderer.render_img's sample placement for a whole frame (src/render.py:177-236 -> :73-171 per ray batch) in two
+ * launches: the rays of every pixel p = y W + x from the pose -- rays_o = t, rays_d = ((x-cx)/fx, (y-cy)/fy, 1) R^T
+ * (build_all_rays with nerf_coordinate = False; c2w DEVICE f32 [4,4]) -> rays_o, rays_d f32 [H W, 3] -- and the
+ * samples of gs_render_sample, bit for bit, with the reference's per-batch semantics: ray batch b = pixels
+ * [b B, (b+1) B) (B = ray_batch) clamps its far bound and places its invalid-depth surface samples with ITS OWN
+ * gt_depth maximum (one segmented-max launch, NaN propagated as torch.max; written to batch_max f32 [ceil(HW/B)]) and
+ * uses perturbation row b of perturb f32 [ceil(HW/B), n_samples] (NULL: no perturbation).  gt_depth f32 [H W] or
+ * NULL (then no surface samples, near 0.01: render_batch_ray's no-depth branch).  n_samples, n_surface <= 64.
+ *   -> z_vals, dists f32 [H W, n_samples + n_surface (0 without depth)].                                      */
+int gs_render_img_sample(const float* c2w, int H, int W, float fx, float fy, float cx, float cy,
+                         const float* gt_depth, const float* bound, const float* t_samples, const float* t_surface,
+                         const float* perturb, int ray_batch, float* rays_o, float* rays_d, float* batch_max,
+                         float* z_vals, float* dists, int n_samples, int n_surface, gs_stream_t stream);
+
+/* Visualizer.vis's image metrics (src/image_visualization.py:57-83) in one deterministic reduction (fp64 partials,
+ * fixed order, no atomics): from color f32 [n,3], depth f32 [n], normal f32 [n,3], sdf f32 [n*s], gt_depth f32 [n],
+ * gt_color f32 [n,3] and c2w DEVICE f32 [4,4]:
+ *   normal_cam f32 [n,3] = R^T normal (camera frame); depth_res f32 [n] = |gt - depth|, color_res f32 [n,3] =
+ *   |gt_color - color|, both 0 where gt < 1e-3;
+ *   metrics f64 [8] = { colour MSE over the k x 3 values with gt > 1e-3, PSNR = -10 log10(MSE), depth MAE, depth
+ *   RMSE (same pixels), fraction of |sdf| < 0.01, fraction of |sdf| < 0.02 (all n s values), k, n s }
+ *   (NaN where k = 0).  Any image output may be NULL.  partial: workspace of gs_render_img_metrics_workspace_bytes(). */
+size_t gs_render_img_metrics_workspace_bytes(void);
+int gs_render_img_metrics(const float* color, const float* depth, const float* normal, const float* sdf,
+                          const float* gt_depth, const float* gt_color, const float* c2w, int n, int s,
+                          float* normal_cam, float* depth_res, float* color_res, double* metrics,
+                          void* workspace, size_t workspace_bytes, gs_stream_t stream);
+
 /* Backward of InstantNeuS.forward, stage 1 (per ray): from the upstream gradients of the ray
  * outputs -- d_color [n,3], d_depth [n], d_depth_var [n], d_normal [n,3], d_weight_sum [n] --
  * and the saved per-point alpha / rgb / z_mid / grad / mask, produce d_alpha f32 [n,s] (w.r.t. the
