@@ -98,11 +98,12 @@ __global__ __launch_bounds__(256) void map_adamw_kernel(AdamArgs A) {
     A.bc1 = 1.0f - powf(A.beta1, t);
     A.bc2_sqrt = sqrtf(1.0f - powf(A.beta2, t));
   }
-  // torch.nn.utils.clip_grad_norm_: coef = max_norm / (total_norm + 1e-6), clamped to 1
+  // torch.nn.utils.clip_grad_norm_: coef = max_norm / (total_norm + 1e-6), clamped to 1 by torch.clamp, which keeps a
+  // NaN (a NaN norm makes every parameter NaN there, so it does here: `c < 1 ? c : 1` would step unclipped)
   float coef = 1.0f;
   if (A.sqnorm) {
     const float c = A.max_norm / (sqrtf(*A.sqnorm) + 1e-6f);
-    coef = c < 1.0f ? c : 1.0f;
+    coef = (c < 1.0f || c != c) ? c : 1.0f;
   }
   const float s16 = A.inv_scale16 * coef;
   const size_t n8 = A.n16 / 8;
@@ -239,11 +240,15 @@ __global__ __launch_bounds__(1024) void map_step_prep_kernel(const float* __rest
                                                              const int* __restrict__ frag_index,
                                                              _Float16* __restrict__ mlp_wpack) {
   __shared__ float red_c[16], red_m[16], bc[3];
+  __shared__ int red_nan[16];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   if (counts_in) {
     if (tid < 3) bc[tid] = counts_in[tid];
   } else {
+    // the maximum is NaN if any depth is NaN (`rays_depth.max()`, as the sampler and the sharded path take it): fmaxf
+    // drops NaN, so a flag rides along, OR-ed across the waves
     float c = 0.f, mx = -INFINITY;
+    int isnan_ = 0;
     for (int i0 = tid; i0 < n; i0 += 1024 * 8) {       // eight loads in flight (a count and a maximum: any order)
       float d8[8];
 #pragma unroll
@@ -252,17 +257,22 @@ __global__ __launch_bounds__(1024) void map_step_prep_kernel(const float* __rest
       for (int u = 0; u < 8; ++u) {
         c += d8[u] > 0.f ? 1.0f : 0.0f;
         mx = fmaxf(mx, d8[u]);
+        isnan_ |= (d8[u] != d8[u]) ? 1 : 0;
       }
     }
     c = gs_wave_sum(c);
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-    if (lane == 0) { red_c[wv] = c; red_m[wv] = mx; }
+    for (int off = 32; off > 0; off >>= 1) {
+      mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+      isnan_ |= __shfl_xor(isnan_, off, 64);
+    }
+    if (lane == 0) { red_c[wv] = c; red_m[wv] = mx; red_nan[wv] = isnan_; }
     __syncthreads();
     if (tid == 0) {
       float cs = 0.f, ms = -INFINITY;
-      for (int k = 0; k < 16; ++k) { cs += red_c[k]; ms = fmaxf(ms, red_m[k]); }
-      bc[0] = cs; bc[1] = (float)n; bc[2] = n > 0 ? ms : 0.0f;
+      int ns = 0;
+      for (int k = 0; k < 16; ++k) { cs += red_c[k]; ms = fmaxf(ms, red_m[k]); ns |= red_nan[k]; }
+      bc[0] = cs; bc[1] = (float)n; bc[2] = n > 0 ? (ns ? NAN : ms) : 0.0f;
     }
   }
   __syncthreads();

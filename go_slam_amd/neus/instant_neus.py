@@ -485,6 +485,16 @@ class _NeusRenderFn(torch.autograd.Function):
         return (None, d_o, d_d, None, None, grid_grad, g["sdf_w"], g["sdf_b"], g["cB"], g["mlp"], g["var"].reshape(()))
 
 
+def _gram_dense_grads(G):
+    """d sdf_layer.weight [32,35], d sdf_layer.bias [32], d color_B [3,33] from the summed, unscaled Gram product
+    G = rows[:, :40]^T rows [40,160] (only the blocks read here are defined; gs_map_step_post reads the same entries)"""
+    g_sdf_w = G[0:32, 40:75].clone()
+    g_sdf_w[0] += G[35, 80:115]                         # column sums of dw0 (row 35 = the ones column)
+    g_sdf_b = G[35, 0:32].clone()
+    g_cB = G[32:35, 120:153].clone()
+    return g_sdf_w, g_sdf_b, g_cB
+
+
 def _neus_backward_raw(model, S, inputs, inv_s, var, d_color, d_depth, d_dvar, d_normal, d_wsum, d_sdf, d_gerr,
                        inv_s_dev=None, var_dev=None, grid_acc_out=None, raw_dense=None, after_table=None,
                        ray_grad_out=None):
@@ -600,11 +610,7 @@ def _neus_backward_raw(model, S, inputs, inv_s, var, d_color, d_depth, d_dvar, d
         _lib.check(L.gs_map_gram(_lib.ptr(rows), np_pad, _lib.ptr(gram), st), "map_gram")
     if raw_dense is not None:       # everything after the Gram partials happens in gs_map_step_post
         return {"grid_acc": grid_acc, "grid_scale": gscale, "gram": gram, "mlp_partial": partial, "loss_scale": LS}
-    G = gram.sum(0) / LS                                # [40,160], fp32 (only the blocks read below are defined)
-    g_sdf_w = G[0:32, 40:75].clone()
-    g_sdf_w[0] += G[35, 80:115]                         # column sums of dw0 (row 35 = the ones column)
-    g_sdf_b = G[35, 0:32].clone()
-    g_cB = G[32:35, 120:153].clone()
+    g_sdf_w, g_sdf_b, g_cB = _gram_dense_grads(gram.sum(0) / LS)
     sf = model.variance_network.scale_factor
     if inv_s_dev is not None:       # device-scalar form: no host value of the variance exists in this step
         raw_d = torch.exp(var_dev.detach().float() * sf)

@@ -287,7 +287,8 @@ int gs_mapping_loss(const float* color, const float* depth, const float* depth_v
  * [hash table (n16 entries) | dense parameters (n - n16)], in two launches.
  *   gs_map_grad_sqnorm: sqnorm_out[0] += sum g^2 (zero it first) over the table gradient g16 (fp16 holding
  *     gradient / inv_scale16, tiny-cuda-nn's loss-scaled form; n16 elements) and the dense gradients g32 (fp32).
- *   gs_map_adamw: coef = min(1, max_norm / (sqrt(sqnorm[0]) + 1e-6)) (sqnorm == NULL: no clipping), then for every
+ *   gs_map_adamw: coef = min(1, max_norm / (sqrt(sqnorm[0]) + 1e-6)) (sqnorm == NULL: no clipping; a NaN sqnorm gives
+ *     a NaN coef, as torch.clamp does in clip_grad_norm_), then for every
  *     element g' = g * coef, p *= 1 - lr wd, m = b1 m + (1 - b1) g', v = b2 v + (1 - b2) g'^2,
  *     p -= lr / (1 - b1^step) * m / (sqrt(v) / sqrt(1 - b2^step) + eps)   (torch.optim.AdamW), lr = lr16 on the table
  *     and lr32 on the dense range; p16 (optional, fp16 [n]) receives the fp16 working copy of the new parameters.
@@ -308,7 +309,8 @@ int gs_map_adamw_seg(float* p, float* m, float* v, void* p16, const void* g16, s
                      const float* sqnorm, float max_norm, gs_stream_t stream);
 
 /* The scalar / reduction arithmetic around the mapper step's kernels in two launches (map_opt.hip):
- *   gs_map_step_prep: counts_out = counts_in if given, else [#rays with depth > 0, n, max depth] of rays_depth [n];
+ *   gs_map_step_prep: counts_out = counts_in if given, else [#rays with depth > 0, n, max depth] of rays_depth [n]
+ *     (max depth = 0 for n = 0, NaN if any depth is NaN, as torch.max);
  *     inv_s_out[0] = clamp(exp(variance[0] * scale_factor), 1e-6, 1e6); d_gerr_out[0:n] = w_eikonal / (counts[1] * samples);
  *     d_invs[0] = sqnorm[0] = 0; step_dev[0] += 1; sdf_wt_out[l][f][o] = sdf_w[o][3 + 2 l + f] (both optional);
  *     mlp_wpack_out[i] = frag_index[i] == 10240 ? 0 : mlp16[frag_index[i]] for i < 20480 (all three optional): the
@@ -319,9 +321,11 @@ int gs_map_adamw_seg(float* p, float* m, float* v, void* p16, const void* g16, s
  *     backward's workgroup partials (f32 [nb,10240]), d inv_s, and loss = sum(loss_rays) + w_eikonal * sum(gerr) /
  *     (counts[1] * samples).                                                                                        */
 /* rows[:, :40]^T rows of the backward's per-point rows (f16 [n_rows,160], n_rows % 16 == 0, zero rows as padding) on the
- * matrix cores: partial f32 [gs_map_gram_blocks(n_rows)][40][160], one slab per workgroup, only the entries
- * gs_map_step_post reads are written (rows 0..31 x columns 32..95, rows 32..39 x all columns) -- pass it as that
- * function's gram_chunks with nchunk = gs_map_gram_blocks(n_rows).  Replaces a batched library GEMM.               */
+ * matrix cores: partial f32 [gs_map_gram_blocks(n_rows)][40][160], one slab per workgroup (workgroup b sums the groups of
+ * 16 rows [b per, min(n_rows / 16, (b + 1) per)), per = ceil(n_rows / 16 / blocks): trailing workgroups may be empty and
+ * write zeros), in a fixed order (two runs are bit-equal).  Only the entries gs_map_step_post reads are written: rows
+ * 0..31 x columns 32..95 and rows 32..39 x columns 0..31 and 64..159 (rows 32..39 x columns 32..63 are not formed) --
+ * pass it as that function's gram_chunks with nchunk = gs_map_gram_blocks(n_rows).  Replaces a batched library GEMM. */
 int gs_map_gram_blocks(int n_rows);
 int gs_map_gram(const void* rows, int n_rows, float* partial, gs_stream_t stream);
 int gs_map_step_prep(const float* rays_depth, int n, const float* variance, float scale_factor, float w_eikonal,

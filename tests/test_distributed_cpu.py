@@ -115,7 +115,8 @@ class _TorchOptKernels:
 
     def adamw(self, p, m, v, p16, g16, inv_scale16, pd, md, vd, p16d, g32, h, step, step_dev, sqnorm):
         t = int(step_dev.item())
-        coef = min(1.0, h["max_norm"] / (float(sqnorm.sqrt()) + 1e-6))
+        c = h["max_norm"] / (float(sqnorm.sqrt()) + 1e-6)
+        coef = c if (c < 1.0 or c != c) else 1.0              # torch.clamp(max=1) keeps a NaN, min(1.0, nan) would not
         for P, M, V, P16, g, lr in ((p, m, v, p16, g16.float() * (inv_scale16 * coef), h["lr16"]),
                                     (pd, md, vd, p16d, g32 * coef, h["lr32"])):
             P.mul_(1 - lr * h["wd"])
