@@ -485,12 +485,8 @@ void neus_mlp_bwd_kernel(const _Float16* __restrict__ X, const _Float16* __restr
 }
 
 // points per wave and loop iteration: two 32-point sub-blocks once every wave of the chip has at least two iterations
-// of them; below that (and in tools' A/B runs: GS_MLP_BWD_NSUB = 1 / 2) single sub-blocks quantise better
-int mlp_bwd_nsub(int n) {
-  static const int forced = [] { const char* e = getenv("GS_MLP_BWD_NSUB"); return e ? atoi(e) : 0; }();
-  if (forced == 1 || forced == 2) return forced;
-  return n >= 2 * 64 * 1024 ? 2 : 1;
-}
+// of them; below that single sub-blocks quantise better
+int mlp_bwd_nsub(int n) { return n >= 2 * 64 * 1024 ? 2 : 1; }
 
 }  // namespace
 

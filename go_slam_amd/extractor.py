@@ -14,8 +14,6 @@ What this module adds for MI355X:
     `relu(skip + y)` -- in the three launches of `gs_norm_act` (csrc/instnorm.hip; one without the norm) instead of
     torch's 6-8 including the bias add: 200 launches per input frame become ~115, with the rounding points of the fp16 tensors the reference materialises.
 """
-import os
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -24,8 +22,8 @@ DIM = 32
 FAST_ENCODER = True         # module constant, not an environment switch: tests flip it to compare the two paths
 OWN_ENC_CONV = True         # gs_enc_conv for the encoder's convolutions (False: MIOpen NHWC fp16, the tests' referee)
 # the inference path as ONE hipGraph per (input shape, weight version): ~60 launches of 3-17 us per input frame replayed
-# back to back instead of enqueued one by one (GOSLAM_ENCODER_GRAPHS=0: always eager)
-ENCODER_GRAPHS = os.environ.get("GOSLAM_ENCODER_GRAPHS", "1") != "0"
+# back to back instead of enqueued one by one (False: always eager)
+ENCODER_GRAPHS = True
 _ENC_SHAPES = {(7, 4, 32, 2), (3, 32, 32, 1), (3, 32, 64, 2), (3, 64, 64, 1), (3, 64, 128, 2), (3, 128, 128, 1),
                (1, 32, 64, 2), (1, 64, 128, 2), (1, 128, 128, 1), (1, 128, 256, 1)}    # (k, c_in, c_out, stride) built
 

@@ -5,16 +5,10 @@ update() = reproject (HIP) -> motion features -> 4-level corr lookup (HIP, one l
 UpdateModule (gs_conv3x3 / MIOpen convolutions + HIP epilogues) -> dense BA (HIP, no host round trips) -> convex
 upsampling.
 """
-import os
-
 import numpy as np
 import torch
 
 from .corr import AltCorrBlock, CorrBlock, CorrPool
-
-# FactorGraph.update: keep the BA's index tables per edge set (GS_BA_REUSE_TABLES); 0 = rebuild them in every call
-BA_TABLES = os.environ.get("GOSLAM_BA_TABLES", "1") == "1"
-
 
 def coords_grid(ht, wd, device):
     y, x = torch.meshgrid(torch.arange(ht, device=device).float(), torch.arange(wd, device=device).float(),
@@ -47,8 +41,6 @@ def upload_tables(host, device):
     out = dict(host)
     if torch.device(device).type == "cpu":
         return out
-    if os.environ.get("GOSLAM_BATCH_UPLOADS", "1") == "0":      # (A/B runs: one blocking copy per table, the round-5 form)
-        return {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in host.items()}
     groups = {}
     for k, v in host.items():
         if torch.is_tensor(v):
@@ -501,7 +493,7 @@ class FactorGraph:
             damping = 0.2 * self.damping[idx["damping_index"]].contiguous() + EPS
 
         # (the cached edge index also keeps the BA's index tables: built by the first call on this edge set, reused after)
-        tables = idx.setdefault("ba_tables", {}) if (BA_TABLES and getattr(self.video, "ba_accepts_tables", False)) else None
+        tables = idx.setdefault("ba_tables", {}) if getattr(self.video, "ba_accepts_tables", False) else None
         if tables is None:
             self.video.ba(target, weight, damping, idx["ii"], idx["jj"], t0=t0, t1=t1, iters=iters,
                           lm=1e-4, ep=0.1, motion_only=motion_only)
@@ -648,8 +640,7 @@ class FactorGraph:
             lm, ep = (1e-4, 1e-1) if ba_type == "loop" else (1e-5, 1e-2)
             # (the cached chunk index also keeps the BA's index tables, as update()'s edge index does: built by the first step
             # on this edge set -- ba_prep_kernel, 183 us at 1200 edges -- and reused by the other steps of the invocation)
-            kw = {"tables": idx.setdefault("ba_tables", {})} if (BA_TABLES and getattr(self.video, "ba_accepts_tables", False)) \
-                else {}
+            kw = {"tables": idx.setdefault("ba_tables", {})} if getattr(self.video, "ba_accepts_tables", False) else {}
             self.video.ba(target, weight, damping, ii_all, jj_all, t0=t0, t1=t1,
                           iters=iters, lm=lm, ep=ep, motion_only=motion_only, ba_type=ba_type, **kw)
             self.video.dirty[:t] = True

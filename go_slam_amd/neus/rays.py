@@ -1,8 +1,6 @@
 """Ray generation for the mapper (reference src/nerf_func.py:115-181 `build_rays`): random pixel
 pick (mask-aware) and ray directions d = K^-1 [u, v, 1] R^T, o = t.  Negligible cost
 (SURVEY.md 8 a11): stays PyTorch, RNG stays on the host side of the kernels."""
-import os
-
 import numpy as np
 import torch
 
@@ -74,7 +72,7 @@ class RayBank:
         cums = torch.stack(mask, 0).to(torch.int64).cumsum(1)               # rank of every valid pixel, 1-based
         self.N = [int(n) for n in cums[:, -1].tolist()]                     # the ONE host transfer of a Mapper call
         # the device draw (gs_ray_draw: one launch per iteration) wants fp32 planes it can index and 32-bit running sums
-        self.fused = (os.environ.get("GOSLAM_RAY_DRAW_FUSED", "1") != "0" and self.color.is_cuda and self.color.dtype == torch.float32 and self.depth.dtype == torch.float32
+        self.fused = (self.color.is_cuda and self.color.dtype == torch.float32 and self.depth.dtype == torch.float32
                       and c2w.dtype == torch.float32 and HW < 2 ** 31)
         if self.fused:
             self.color, self.depth = self.color.contiguous(), self.depth.contiguous()

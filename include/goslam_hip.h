@@ -410,8 +410,7 @@ int gs_ba_ex(float* poses, float* disps, const float* intrinsics, const float* d
  *   path: 0 = gs_ba's own choice by n, 1 = the one-workgroup LDS path (n <= 192, n % 6 == 0), 2 = the one-workgroup
  *     path with global head stages (n % 6 == 0, n <= 300), 3 = the blocked multi-launch path (any n >= 1).  A forced
  *     path whose limits n does not meet is refused with GS_ERR_UNSUPPORTED before anything is enqueued.
- *   status: device int32[4]; [0] = 1 if this solve failed, else 0; [1] += 1 per failed solve; [2..3] scratch of the
- *     solver (gs_ba's own header words).                                                                           */
+ *   status: device int32[4]; [0] = 1 if this solve failed, else 0; [1] += 1 per failed solve; [2..3] reserved.      */
 int gs_chol_solve(double* H, double* b, int n, float lm, float ep, int path, float* dx, int32_t* status,
                   gs_stream_t stream);
 

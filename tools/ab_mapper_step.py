@@ -1,6 +1,6 @@
 """Wall time of the fused mapper step (hipGraph replay) at 4096 and 32768 rays, plus a checksum of the trained state, for
-same-box A/B runs of a knob or a second library build:
-    GOSLAM_FORK_BIN_REDUCE=0 python tools/ab_mapper_step.py ; GOSLAM_FORK_BIN_REDUCE=1 python tools/ab_mapper_step.py
+same-box A/B runs of a second library build (GOSLAM_HIP_LIB) or of a second checkout:
+    python tools/ab_mapper_step.py ; GOSLAM_HIP_LIB=/path/to/other/libgoslam_hip.so python tools/ab_mapper_step.py
 Prints one JSON line: ms per step (median of 5 blocks of `iters` steps) and an exact checksum of the table after the run
 (two variants that launch the same kernels in a different order must print the same checksum)."""
 import json
@@ -16,7 +16,7 @@ from go_slam_amd.neus.mapper import MapTrainer      # noqa: E402
 
 iters = int(sys.argv[1]) if len(sys.argv) > 1 else 30
 dev = torch.device("cuda:0")
-out = {"fork": os.environ.get("GOSLAM_FORK_BIN_REDUCE", "1"), "lib": os.environ.get("GOSLAM_HIP_LIB", "")}
+out = {"lib": os.environ.get("GOSLAM_HIP_LIB", "")}
 for n in (4096, 32768):
     g = torch.Generator().manual_seed(43)
     model = neus.InstantNeuS({}, [[-5.0, 5.0]] * 3).to(dev)

@@ -2,7 +2,7 @@
 
     python tools/mlp_bwd_check.py [--points 2359296 294912] [--out profiles/r06_mlp_bwd.json]
 
-Run on the GPU box.  GS_MLP_BWD_NSUB=1|2 in the environment forces the kernel's points-per-iteration (A/B runs).
+Run on the GPU box.
 The comparison is a development aid (the parity tests are tests/test_neus_gpu.py: autograd on the oracle's network and
 the reference module's own gradients); the timing is what profiles/ records.
 """
@@ -97,7 +97,7 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
-    out = {"forced_nsub": os.environ.get("GS_MLP_BWD_NSUB"), "runs": [run(n, dev) for n in a.points]}
+    out = {"runs": [run(n, dev) for n in a.points]}
     print(json.dumps(out))
     if a.out:
         with open(a.out, "w") as f:

@@ -1,4 +1,5 @@
-"""bench.py's end-to-end sequence legs as a stand-alone command (same-box A/B runs of a knob):
+"""bench.py's end-to-end sequence legs as a stand-alone command (same-box A/B runs of a second library build
+through GOSLAM_HIP_LIB, or of a second checkout):
     python tools/sequence_ab.py [plain] [loop] [sparse]
 Prints one JSON line per leg: frontend ms per keyframe, MotionFilter ms per frame, frames per second, mean edges."""
 import json
@@ -18,4 +19,4 @@ for leg in legs:
     out = bench.sequence_bench(dev, **kw[leg])
     keep = {k: out[k] for k in out if k in ("frontend_e2e_ms_per_keyframe", "motion_filter_ms_per_frame", "frames_per_s",
                                              "edges_mean", "six_update_unit_ms_on_the_final_graph", "e2e_over_unit")}
-    print(json.dumps({"leg": leg, "batch_uploads": os.environ.get("GOSLAM_BATCH_UPLOADS", "1"), **keep}))
+    print(json.dumps({"leg": leg, **keep}))
