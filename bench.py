@@ -16,10 +16,12 @@ no WORLD_SIZE, the script re-executes itself under `torch.distributed.run --nnod
 --master-addr 127.0.0.1` and passes rank 0's JSON line through; `n_gpus` is the RCCL world size either way and
 `rccl_ranks` is the sum of ones the ranks all-reduced on their devices.
 
-Extra objects on the line: `roofline` for the time-dominant hand-written kernel (the update
-operator's implicit-GEMM 3x3 convolution, MFMA-bound: algorithmic FLOPs / launch time measured with
-events on the launch stream; the HBM-bound lookup / volume kernels are in `roofline_other`) and `cpu_baseline` (the CPU oracle + the same UpdateModule on the host cores,
-on a bounded 1-update sample, rank 0 at N=1 only).
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the headline line.  With --full
+it then runs every other leg and adds its objects to the line (rank 0): `roofline` for the time-dominant hand-written
+kernel (the update operator's implicit-GEMM 3x3 convolution, MFMA-bound: algorithmic FLOPs / launch time measured with
+events on the launch stream; the HBM-bound lookup / volume kernels are in `roofline_other`), `cpu_baseline` (the CPU
+oracle + the same UpdateModule on the host cores, on a bounded 1-update sample, N=1 only), the NeuS mapping and
+render legs, the end-to-end sequences, the global-BA legs and `summary`.
 """
 import argparse
 import json
@@ -1069,7 +1071,9 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other leg (NeuS, rooflines, sequences, CPU baselines, ...)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline legs")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the timed step's outputs after its last step to DIR/<name>.npy (float32)")
     args = ap.parse_args()
@@ -1158,6 +1162,20 @@ def main():
         "updates_per_s": value * UPDATES_PER_KF, "state_finite": finite,
         "rccl_ranks": rccl_ranks, "collective_backend": backend,
     }
+    if args.full:
+        full_legs(args, line, device, rank, world, distributed, video, update_op, graph)
+    if distributed:
+        dist.barrier()
+        dist.destroy_process_group()
+    flush_c_stdio()                             # every C-level byte of this process is out before the line is printed:
+    sys.stdout.flush()                          # the line stays the ONLY line of stdout
+    os.dup2(line_fd, 1)
+    if rank == 0:
+        print(json.dumps(line), flush=True)
+
+
+def full_legs(args, line, device, rank, world, distributed, video, update_op, graph):
+    """--full: every measurement beyond the headline, after its timed region and dump, into `line` (rank 0's keys)."""
     # collective legs: every rank takes part.  With N > 1 the exact collective calls of the sharded mapper step are first
     # issued on small tensors and the ranks agree on the outcome -- a launcher / RCCL problem in that path must cost the
     # path-M legs of the line, never the tracking headline above (tracking does not communicate).
@@ -1284,14 +1302,6 @@ def main():
         if "altcorr_roofline" in st:
             line["roofline_other"].append(st["altcorr_roofline"])
         line["summary"] = summary(line)         # LAST key: a reader of the line's tail sees every leg's headline number
-    if distributed:
-        dist.barrier()
-        dist.destroy_process_group()
-    flush_c_stdio()                             # every C-level byte of this process is out before the line is printed:
-    sys.stdout.flush()                          # the line stays the ONLY line of stdout
-    os.dup2(line_fd, 1)
-    if rank == 0:
-        print(json.dumps(line), flush=True)
 
 
 if __name__ == "__main__":

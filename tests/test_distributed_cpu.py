@@ -103,6 +103,26 @@ def test_bench_gpus_flag_spawns_that_many_ranks():
     assert json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][0])["n_gpus"] == 1
 
 
+def test_bench_full_flag_reaches_every_rank():
+    """`--full` (every leg beyond the headline) is an option of its own, off by default, and a self-launched run hands
+    it to each rank it starts: every rank parses it (an unknown option would end that rank with status 2)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--help"], stdout=subprocess.PIPE,
+                         stderr=subprocess.PIPE, text=True, timeout=120)
+    assert res.returncode == 0 and "--full" in res.stdout, res.stderr[-2000:]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    env["GS_BENCH_LAUNCH_ONLY"] = "1"
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
+                          "--full"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=240)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1 and json.loads(lines[0])["rccl_ranks"] == 2, res.stdout
+
+
 # ---- sharded optimiser (FlatAdamW with world > 1): reduce-scatter -> slice step -> all-gather -----------------------
 class _TorchOptKernels:
     """torch restatement of csrc/map_opt.hip's two kernels (TEST infrastructure: lets the gloo test drive the sharding

@@ -11,11 +11,11 @@ mkdir -p $OUT
 cd $R
 ( time timeout 1500 python -m pytest tests -m gpu -q ) > $OUT/pytest_gpu.log 2>&1
 tail -6 $OUT/pytest_gpu.log
-timeout 900 python bench.py --steps 20 --warmup 5 2> $OUT/bench.err | tail -1 > $OUT/bench.json
+timeout 900 python bench.py --full --steps 20 --warmup 5 2> $OUT/bench.err | tail -1 > $OUT/bench.json
 tail -c 1900 $OUT/bench.json; echo
 # the N > 1 code path of bench.py on this 1-GPU box: 2 ranks on cuda:0, gloo carrying the collectives (functional smoke
 # run of the sharded step + the per-rank exchange timing; never used for numbers)
-GS_BENCH_SMOKE_ONE_GPU=1 timeout 600 python bench.py --gpus 2 --steps 2 --warmup 1 --no-cpu-baseline 2> $OUT/bench_2ranks.err | tail -1 > $OUT/bench_2ranks_smoke.json
+GS_BENCH_SMOKE_ONE_GPU=1 timeout 600 python bench.py --full --gpus 2 --steps 2 --warmup 1 --no-cpu-baseline 2> $OUT/bench_2ranks.err | tail -1 > $OUT/bench_2ranks_smoke.json
 python - <<PY
 import json
 try:
