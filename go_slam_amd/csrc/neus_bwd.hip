@@ -33,7 +33,8 @@
 //           ds_add_f32: 2.2 ms; a barrier-synchronised non-atomic version: 5.3 ms).
 // The dense levels 0-4 (0.5 M entries, heavily pre-reduced inside the wave) stay on packed atomics.  Overflow of a
 // staging bin or of a queue falls back to the atomic, so every input is handled.  Side effect: the hashed levels'
-// gradient is summed in fp32 (each record rounded once to fp16) instead of through thousands of fp16 read-modify-writes.
+// gradient is summed exactly (each record rounded once to fp16, the sum once) instead of through thousands of fp16
+// read-modify-writes.
 #include "common.h"
 #include "neus_common.h"
 #include <math.h>
@@ -112,14 +113,18 @@ __global__ __launch_bounds__(256) void neus_ray_bwd_kernel(
     dLdw[h] = on[h] ? v : 0.0f;
     u[h] = dLdw[h] * w[h];
   }
-  // R_k = sum_{j>k} u_j  (suffix over the 128 virtual positions, second half first)
+  // R_k = sum_{j>k} u_j  (suffix over the 128 virtual positions, second half first), taken as the NEXT lane's inclusive
+  // sum.  (inc_k - u_k cancels when sample k is opaque: R_k is ~(1 - a_k + 1e-7) u_k, so the rounding error of inc_k,
+  // 2^-24 u_k, divided by 1 - a_k + 1e-7 ~ 1e-7 made d_alpha_k wrong by O(1) -- sign included; tests/
+  // test_neus_bwd_numerics_gpu.py, regimes one_opaque / near_one.)
   float R[2];
   {
     const float inc1 = wave_incl_suffix_sum(u[1], lane);
-    R[1] = inc1 - u[1];
     const float tot1 = __shfl(inc1, 0, 64);
     const float inc0 = wave_incl_suffix_sum(u[0], lane);
-    R[0] = (inc0 - u[0]) + tot1;
+    const float nx1 = __shfl_down(inc1, 1, 64), nx0 = __shfl_down(inc0, 1, 64);
+    R[1] = lane < 63 ? nx1 : 0.0f;
+    R[0] = (lane < 63 ? nx0 : 0.0f) + tot1;
   }
 #pragma unroll
   for (int h = 0; h < 2; ++h) {

@@ -222,7 +222,8 @@ int gs_neus_backward_points(const float* rays_o, const float* rays_d, const floa
                             int row_stride, float* d_inv_s, int n, int s, const void* enc_aux, gs_stream_t stream);
 /* The same backward with the table gradient of the HASHED levels accumulated WITHOUT global atomics (bin-and-reduce:
  * workgroups write (13-bit index, 2 x fp16) records to their own segments of per-(level, bin) queues in `bin_ws`, then
- * one workgroup per bin sums its queue in fp32 LDS accumulators and writes its 8192 entries once; neus_bwd.hip).
+ * one workgroup per bin sums its queue exactly in 64-bit fixed-point LDS accumulators (every fp16 record is a multiple of
+ * 2^-24), rounds each sum to fp16 once and writes its 8192 entries once; neus_bwd.hip grid_bin_reduce_kernel).
  * grid_grad is the loss-scaled f16 table gradient (zero it first; the dense levels and any overflow records still
  * arrive as packed atomics).  `bin_ws`: gs_neus_bin_workspace_bytes(n * s) bytes of scratch (no initial state).
  * `sdf_wt` (optional, f32 [16][2][32]): sdf_w's encoding columns transposed, sdf_wt[l][f][o] = sdf_w[o][3 + 2 l + f]

@@ -979,9 +979,9 @@ def _grid_grads(N, O, dev, P, rays, binned, grad_dtype):
 
 
 def test_binned_table_gradient_equals_atomic_accumulation(N, O, dev):
-    """The hashed levels' table gradient by bin-and-reduce (no global atomics: per-bin record queues + fp32 LDS sums,
-    csrc/neus_bwd.hip) vs fp32 atomics on the same rays: equal to fp16 record rounding -- and CLOSER to the fp32 result
-    than tiny-cuda-nn's fp16 packed atomics are."""
+    """The hashed levels' table gradient by bin-and-reduce (no global atomics: per-bin record queues + exact 64-bit
+    fixed-point LDS sums, csrc/neus_bwd.hip grid_bin_reduce_kernel) vs fp32 atomics on the same rays: equal to fp16
+    record rounding -- and CLOSER to the fp32 result than tiny-cuda-nn's fp16 packed atomics are."""
     P = O.make_params(81, grid_init=0.3, bound=((-2.5, 2.5), (-2.5, 2.5), (-2.5, 2.5)))
     o, d, gt = _rays(3000, seed=82)
     g = torch.Generator().manual_seed(83)
