@@ -49,7 +49,12 @@ SIGNATURES = {
     "gs_frame_distance": (c_int, [_P] * 6 + [c_int] * 3 + [c_float, _P]),
     "gs_iproj": (c_int, [_P] * 4 + [c_int] * 3 + [_P]),
     "gs_depth_filter": (c_int, [_P] * 6 + [c_int] * 4 + [_P]),
-    "gs_cvx_upsample": (c_int, [_P] * 4 + [c_int] * 4 + [_P]),
+    "gs_pointcloud_workspace_bytes": (c_size_t, [c_int] * 3),
+    "gs_pointcloud_count": (c_int, [_P] * 5 + [c_float, c_float] + [c_int] * 4 + [_P, c_size_t, _P]),
+    "gs_pointcloud_mask": (c_int, [_P, _P] + [c_int] * 4 + [_P, c_size_t, _P]),
+    "gs_pointcloud_scan": (c_int, [c_int] * 3 + [_P, c_size_t, _P, _P]),
+    "gs_pointcloud_emit": (c_int, [_P] * 5 + [c_int] * 4 + [_P, c_size_t, ctypes.c_longlong, _P, _P, _P]),
+    "gs_cvx_upsample":(c_int, [_P] * 4 + [c_int] * 4 + [_P]),
     "gs_upmask_upsample": (c_int, [_P, c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "gs_bias_act": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "gs_motion_features": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),

@@ -7,18 +7,12 @@
 // recomputed per lane from 14 uniform floats (the compiler keeps them in SGPRs) rather than
 // via a thread-0 prologue + barrier.  Compiled with -ffp-contract=off so that masks, floors
 // and counts agree bit-for-bit with the op-by-op fp32 oracle.
-#include "common.h"
+#include "geom_common.h"
 
 namespace {
 
 constexpr float kMinDepthKernel = 0.25f;   // droid_kernels.cu:26
 constexpr float kMinDepthPy = 0.2f;        // geom/projective_ops.py:4
-
-__device__ __forceinline__ void load_pose(const float* poses, int k, float* t, float* q) {
-  const float* p = poses + (size_t)k * 7;
-  t[0] = p[0]; t[1] = p[1]; t[2] = p[2];
-  q[0] = p[3]; q[1] = p[4]; q[2] = p[5]; q[3] = p[6];
-}
 
 // ---- DepthVideo.reproject (projective_ops.py:114-144, jacobian=False) -------------------
 __global__ __launch_bounds__(256) void reproject_kernel(
@@ -35,8 +29,8 @@ __global__ __launch_bounds__(256) void reproject_kernel(
     qij[0] = 0.f; qij[1] = 0.f; qij[2] = 0.f; qij[3] = 1.f;
   } else {          // Gij = Gj * Gi^-1 with lietorch's group ops
     float ti[3], qi[4], tj[3], qj[4];
-    load_pose(poses, ix, ti, qi);
-    load_pose(poses, jx, tj, qj);
+    gs_load_pose(poses, ix, ti, qi);
+    gs_load_pose(poses, jx, tj, qj);
     float qinv[4] = {-qi[0], -qi[1], -qi[2], qi[3]};
     float r[3], tinv[3];
     gs_act_so3(qinv, ti, r);
@@ -67,8 +61,8 @@ __global__ __launch_bounds__(256) void projmap_kernel(
   if (p >= hw) return;
   const int ix = (int)ii[e], jx = (int)jj[e];
   float ti[3], qi[4], tj[3], qj[4], tij[3], qij[4];
-  load_pose(poses, ix, ti, qi);
-  load_pose(poses, jx, tj, qj);
+  gs_load_pose(poses, ix, ti, qi);
+  gs_load_pose(poses, jx, tj, qj);
   gs_rel_se3(ti, qi, tj, qj, tij, qij);
   const float fx = intr[0], fy = intr[1], cx = intr[2], cy = intr[3];
   const float u = (float)(p % wd), v = (float)(p / wd);
@@ -95,8 +89,8 @@ __global__ __launch_bounds__(256) void frame_distance_kernel(
   const int e = blockIdx.x;
   const int ix = (int)ii[e], jx = (int)jj[e];
   float ti[3], qi[4], tj[3], qj[4], tij[3], qij[4];
-  load_pose(poses, ix, ti, qi);
-  load_pose(poses, jx, tj, qj);
+  gs_load_pose(poses, ix, ti, qi);
+  gs_load_pose(poses, jx, tj, qj);
   gs_rel_se3(ti, qi, tj, qj, tij, qij);
   const float fx = intr[0], fy = intr[1], cx = intr[2], cy = intr[3];
   float accum = 0.f, valid = 0.f;
@@ -141,21 +135,15 @@ __global__ __launch_bounds__(256) void iproj_kernel(
   const int n = blockIdx.y;
   if (p >= hw) return;
   float t[3], q[4];
-  load_pose(poses, n, t, q);
-  const float fx = intr[0], fy = intr[1], cx = intr[2], cy = intr[3];
+  gs_load_pose(poses, n, t, q);
   const float u = (float)(p % wd), v = (float)(p / wd);
-  float Xi[4] = {(u - cx) / fx, (v - cy) / fy, 1.0f, disps[(size_t)n * hw + p]};
-  float Xj[4];
-  gs_act_se3(t, q, Xi, Xj);
-  float* o = points + ((size_t)n * hw + p) * 3;
-  o[0] = Xj[0] / Xj[3];
-  o[1] = Xj[1] / Xj[3];
-  o[2] = Xj[2] / Xj[3];
+  gs_iproj_point(t, q, intr[0], intr[1], intr[2], intr[3], u, v, disps[(size_t)n * hw + p],
+                 points + ((size_t)n * hw + p) * 3);
 }
 
 // ---- depth_filter (droid_kernels.cu:661-775) ---------------------------------------------
-// One lane per pixel loops over the 6 neighbours itself, so the count is a plain register
-// sum (the reference issues one float atomicAdd per neighbour hit).
+// One lane per pixel loops over the 6 neighbours itself (geom_common.h), so the count is a plain register sum (the
+// reference issues one float atomicAdd per neighbour hit).
 __global__ __launch_bounds__(256) void depth_filter_kernel(
     const float* __restrict__ poses, const float* __restrict__ disps, const float* __restrict__ intr,
     const int64_t* __restrict__ inds, const float* __restrict__ thresh, float* __restrict__ counter,
@@ -163,40 +151,8 @@ __global__ __launch_bounds__(256) void depth_filter_kernel(
   const int p = blockIdx.x * 256 + threadIdx.x;
   const int b = blockIdx.y;
   if (p >= hw) return;
-  const int ix = (int)inds[b];
-  const float th = thresh[b];
-  const float fx = intr[0], fy = intr[1], cx = intr[2], cy = intr[3];
-  const float ui = (float)(p % wd), vi = (float)(p / wd);
-  const float di = disps[(size_t)ix * hw + p];
-  float ti[3], qi[4];
-  load_pose(poses, ix, ti, qi);
-  float count = 0.f;
-#pragma unroll
-  for (int neigh = 0; neigh < 6; ++neigh) {
-    const int jx = (neigh < 3) ? ix - neigh - 1 : ix + neigh;
-    if (jx < 0 || jx >= num) continue;
-    float tj[3], qj[4], tij[3], qij[4];
-    load_pose(poses, jx, tj, qj);
-    gs_rel_se3(ti, qi, tj, qj, tij, qij);
-    float Xi[4] = {(ui - cx) / fx, (vi - cy) / fy, 1.0f, di};
-    float Xj[4];
-    gs_act_se3(tij, qij, Xi, Xj);
-    const float uj = fx * (Xj[0] / Xj[2]) + cx;
-    const float vj = fy * (Xj[1] / Xj[2]) + cy;
-    const float dj = Xj[3] / Xj[2];
-    const float fu = floorf(uj), fv = floorf(vj);
-    if (fu >= 0.f && fv >= 0.f && fu < (float)(wd - 1) && fv < (float)(ht - 1)) {
-      const int u0 = (int)fu, v0 = (int)fv;
-      const float* dj_map = disps + (size_t)jx * hw + (size_t)v0 * wd + u0;
-      const double inv = 1.0 / (double)dj;
-      const double t = (double)th;
-      if (fabs(inv - 1.0 / (double)dj_map[0]) < t) count += 1.0f;
-      else if (fabs(inv - 1.0 / (double)dj_map[1]) < t) count += 1.0f;
-      else if (fabs(inv - 1.0 / (double)dj_map[wd]) < t) count += 1.0f;
-      else if (fabs(inv - 1.0 / (double)dj_map[wd + 1]) < t) count += 1.0f;
-    }
-  }
-  counter[(size_t)b * hw + p] = count;
+  counter[(size_t)b * hw + p] = gs_depth_filter_count(poses, disps, (int)inds[b], p, intr[0], intr[1], intr[2],
+                                                      intr[3], thresh[b], num, hw, ht, wd);
 }
 
 }  // namespace

@@ -150,3 +150,24 @@ def make_altcorr_chunk(seed=211):
             c = c * 3.0 - 20.0
         coords.append(c)
     return fm, ii, jj, torch.stack(coords)[None].contiguous()
+
+
+def plane_disps(poses, intr, ht, wd):
+    """Inverse depth f32 [B, ht, wd] of a wall z = 4 and a floor y = 1.2 (world frame) seen through world-to-camera
+    poses [B, 7] at full-resolution intrinsics [4], on the poses' device; 0 where neither is hit in front of the camera.
+    Rendered in float64, so neighbouring keyframes agree to fp32 rounding."""
+    from .lietorch_shim import SE3
+    c2w = SE3(poses.double()).inv().data
+    t, q = c2w[:, None, None, :3], c2w[:, None, None, 3:]
+    fx, fy, cx, cy = intr.double().tolist()
+    v, u = torch.meshgrid(torch.arange(ht, dtype=torch.float64, device=poses.device),
+                          torch.arange(wd, dtype=torch.float64, device=poses.device), indexing="ij")
+    ray = torch.stack([(u - cx) / fx, (v - cy) / fy, torch.ones_like(u)], -1).expand(poses.shape[0], -1, -1, -1)
+    qv, w = q[..., :3].expand_as(ray), q[..., 3:]       # camera-to-world rotation of the pixel rays
+    uv = 2.0 * torch.cross(qv, ray, dim=-1)
+    ray = ray + w * uv + torch.cross(qv, uv, dim=-1)
+    best = torch.full(ray.shape[:-1], float("inf"), dtype=torch.float64, device=poses.device)
+    for axis, c in ((2, 4.0), (1, 1.2)):
+        z = (c - t[..., axis]) / ray[..., axis]
+        best = torch.minimum(best, torch.where(z > 0.1, z, torch.full_like(z, float("inf"))))
+    return torch.where(torch.isfinite(best), 1.0 / best, torch.zeros_like(best)).float()

@@ -174,6 +174,34 @@ int gs_depth_filter(const float* poses, const float* disps, const float* intrins
                     const int64_t* ix, const float* thresh, float* counter,
                     int n, int num, int h, int w, gs_stream_t stream);
 
+/* ---- keyframe point cloud (droid_visualization, src/visualization.py:104-150), csrc/pointcloud.hip ----
+ *
+ * The coloured dense cloud of k listed keyframes index i64 [k] (each in [0, num)) of full-resolution buffers
+ * disps f32 [num,h,w] and images f32 [num,3,h,w], written compacted in (list position, row-major pixel) order.
+ * Three launches, no atomics:
+ *   gs_pointcloud_count: keep = (depth_filter count >= visible_num) & (disps[ix] > disp_floor[b]), the count being
+ *                        exactly gs_depth_filter's with thresh for every keyframe (poses f32 [num,7], all num slots as
+ *                        neighbours, intrinsics f32 [4]);
+ *   gs_pointcloud_mask:  instead of the count pass, keep = mask[ix] != 0 (mask f32 [num,h,w]);
+ *   gs_pointcloud_scan:  offsets i64 [k+1] on the device: offsets[b] = first point of list position b,
+ *                        offsets[k] = the total -- the one value the host reads, to size the outputs;
+ *   gs_pointcloud_emit:  points f32 [n_points,3] = gs_iproj's point of the pixel through poses_inv f32 [k,7] (one per
+ *                        list position), colors f32 [n_points,3] = images[ix][:, pixel].  Every store is bounded by
+ *                        n_points (= offsets[k]); nothing is launched when it is 0.
+ * gs_pointcloud_workspace_bytes: transient device memory shared by the three steps, about 1/8 byte per listed pixel
+ *   plus 12 bytes per 1024; 0 for an unsupported shape (k > 65535 or h * w > 2^30).                            */
+size_t gs_pointcloud_workspace_bytes(int k, int h, int w);
+int gs_pointcloud_count(const float* poses, const float* disps, const float* intrinsics, const int64_t* index,
+                        const float* disp_floor, float thresh, float visible_num, int k, int num, int h, int w,
+                        void* workspace, size_t workspace_bytes, gs_stream_t stream);
+int gs_pointcloud_mask(const float* mask, const int64_t* index, int k, int num, int h, int w, void* workspace,
+                       size_t workspace_bytes, gs_stream_t stream);
+int gs_pointcloud_scan(int k, int h, int w, void* workspace, size_t workspace_bytes, long long* offsets,
+                       gs_stream_t stream);
+int gs_pointcloud_emit(const float* poses_inv, const float* disps, const float* intrinsics, const float* images,
+                       const int64_t* index, int k, int num, int h, int w, const void* workspace,
+                       size_t workspace_bytes, long long n_points, float* points, float* colors, gs_stream_t stream);
+
 /* ------------------------------------------- update-operator gate fusions ---- */
 
 /* ConvGRU gates of src/modules/gru.py:20-33 around MIOpen's convolutions; all NHWC fp16.
