@@ -54,6 +54,8 @@ SIGNATURES = {
     "gs_pointcloud_mask": (c_int, [_P, _P] + [c_int] * 4 + [_P, c_size_t, _P]),
     "gs_pointcloud_scan": (c_int, [c_int] * 3 + [_P, c_size_t, _P, _P]),
     "gs_pointcloud_emit": (c_int, [_P] * 5 + [c_int] * 4 + [_P, c_size_t, ctypes.c_longlong, _P, _P, _P]),
+    "gs_frame_prep_color": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "gs_frame_prep_depth": (c_int, [_P, c_int, c_float, c_int, c_int, c_int, c_int, _P]),
     "gs_cvx_upsample":(c_int, [_P] * 4 + [c_int] * 4 + [_P]),
     "gs_upmask_upsample": (c_int, [_P, c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "gs_bias_act": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
@@ -146,6 +148,20 @@ SIGNATURES = {
     "gs_icp_moments_workspace_bytes": (c_size_t, [c_int]),
     "gs_icp_moments": (c_int, [_P, c_int, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
 }
+
+
+class ColorView(ctypes.Structure):
+    """gs_color_view of include/goslam_hip.h."""
+    _fields_ = [("src", c_void_p), ("map_x", c_void_p), ("map_y", c_void_p), ("tmp", c_void_p), ("dst", c_void_p),
+                ("h", c_int), ("w", c_int), ("c", c_int), ("mh", c_int), ("mw", c_int)]
+
+
+class DepthView(ctypes.Structure):
+    """gs_depth_view of include/goslam_hip.h."""
+    _fields_ = [("src", c_void_p), ("dst", c_void_p), ("h", c_int), ("w", c_int)]
+
+
+FRAME_PREP_MAX_VIEWS = 32
 
 
 class GridMeta(ctypes.Structure):

@@ -31,7 +31,9 @@ def _torch_scatter():
     return m
 
 
-def install(droid_backends=True, tinycudann=True, lietorch=True, torch_scatter=True):
+def install(droid_backends=True, tinycudann=True, lietorch=True, torch_scatter=True, datasets=False):
+    """datasets=True also registers go_slam_amd.datasets as `src.datasets`, so the reference's run.py resolves
+    get_dataset here (its own module imports cv2, which this stack lacks)."""
     if droid_backends:
         from . import droid_backends as db
         sys.modules["droid_backends"] = db
@@ -43,3 +45,6 @@ def install(droid_backends=True, tinycudann=True, lietorch=True, torch_scatter=T
         sys.modules["lietorch"] = lietorch_shim
     if torch_scatter and "torch_scatter" not in sys.modules:
         sys.modules["torch_scatter"] = _torch_scatter()
+    if datasets:
+        from . import datasets as ds
+        sys.modules["src.datasets"] = ds

@@ -202,6 +202,39 @@ int gs_pointcloud_emit(const float* poses_inv, const float* disps, const float* 
                        const int64_t* index, int k, int num, int h, int w, const void* workspace,
                        size_t workspace_bytes, long long n_points, float* points, float* colors, gs_stream_t stream);
 
+/* ---- frame preprocessing of the dataset readers (src/datasets.py:96-143, 565-605), csrc/frame_prep.hip ----
+ *
+ * Semantics: tests/frame_prep_restatement.py, bit for bit (cv2.remap / cv2.resize INTER_LINEAR on 8-bit data,
+ * F.interpolate nearest on depth).  Every view is resized to the full frame (H_out + 2 H_edge) x (W_out + 2 W_edge) and
+ * only the window [H_edge, H_edge + H_out) x [W_edge, W_edge + W_out) is computed.
+ *
+ * gs_frame_prep_color: n views, each its own size.  src uint8 [h,w,c] (c = 1: grey, written to all three planes; c = 3:
+ *   RGB, plane k from channel k: the decoder's RGB is the reference's BGR image reversed).  With map_x / map_y f32
+ *   [mh,mw] (both or neither) the view is first remapped (BORDER_CONSTANT 0) into tmp uint8 [mh,mw,c], which is then
+ *   resized.  dst f32 [3,H_out,W_out] = level / 255.0f.
+ *   src and tmp start 4-byte aligned; rows need not.  One launch per GS_FRAME_PREP_MAX_VIEWS views, plus one remap
+ *   launch per such chunk that holds a mapped view.  h, w, mh, mw in [1, 16384], w * c and mw * c at most 16384.
+ * gs_frame_prep_depth: src uint16 [h,w] (4-byte aligned) -> dst f32 [H_out,W_out] = float(level) / scale, nearest
+ *   resize.  One launch per GS_FRAME_PREP_MAX_VIEWS views; w at most 8192.                                          */
+#define GS_FRAME_PREP_MAX_VIEWS 32
+typedef struct {
+  const uint8_t* src;
+  const float* map_x;    /* NULL: no remap */
+  const float* map_y;
+  uint8_t* tmp;          /* [mh,mw,c] when mapped */
+  float* dst;
+  int h, w, c, mh, mw;
+} gs_color_view;
+typedef struct {
+  const uint16_t* src;
+  float* dst;
+  int h, w;
+} gs_depth_view;
+int gs_frame_prep_color(const gs_color_view* views_host, int n, int H_out, int W_out, int H_edge, int W_edge,
+                        gs_stream_t stream);
+int gs_frame_prep_depth(const gs_depth_view* views_host, int n, float scale, int H_out, int W_out, int H_edge,
+                        int W_edge, gs_stream_t stream);
+
 /* ------------------------------------------- update-operator gate fusions ---- */
 
 /* ConvGRU gates of src/modules/gru.py:20-33 around MIOpen's convolutions; all NHWC fp16.
