@@ -443,7 +443,8 @@ __device__ __forceinline__ void normalise_point(const NeusArgs& A, const float p
 // record [enc0, enc1 (fp16) | this level's contribution to d sdf / d view (3 x fp32)], written with non-temporal stores so
 // that the stream does not evict the table; neus_point_kernel consumes the records in level order with the same
 // arithmetic as before (the SDF linear layer is evaluated from the same fp16 encodings in the same order: sdf is
-// bit-identical; the gradient sums one rounded fma chain per level instead of one chain over all levels).
+// bit-identical; so is the gradient: the record holds the level's fmaf(g1, dv1, g0 * dv0), added to the running sum
+// exactly as the point-major loop adds it).
 // Training: the backward's record [enc0, enc1, d enc / dx (6)] fp16 (enc_aux) is written here as well.
 // ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void neus_encode_levels_kernel(NeusArgs A, gs_grid_meta m, u32x4* __restrict__ rec,
