@@ -1,0 +1,361 @@
+"""fp64 restatement of the hash-grid encoding's generic autograd kernels, host only:
+
+  encode      grid_encode_kernel / grid_level (go_slam_amd/csrc/neus.hip, gs_grid_encode): out f16 [n,32], dy_dx f32 [n,32,3]
+  backward    grid_backward_kernel<SECOND> (go_slam_amd/csrc/grid_autograd.hip, gs_grid_backward): first order (v is None)
+              dx and the table gradient; second order (v = d L / d (dx)) ddy, the mixed second derivatives in dx and the
+              directional-derivative table gradient
+
+Both are evaluated in float64 from the kernels' own fp32 / fp16 operands, in the kernels' operation order, with a running
+error bound beside every value (class E and the add / sub / mul / fma / round16 of tests/neus_bwd_restatement.py, which
+this module imports: an fp32 operation adds u (|result| + bound) to what its operands propagate).
+
+  * Cell coordinates: pos = fmaf(scale, x, 0.5) (one rounding; the library is built with -ffp-contract=off), floor and
+    f = pos - floor are restated in fp32 operation by operation (neus_bwd_restatement.cells), so the cell of a point on a
+    cell face (f = 0) is decided exactly as the kernel decides it.  1 - f is an fp32 subtraction and carries its rounding.
+  * out: the fp32 value (8 fmas over the corner weights ((w0 w1) w2)) within its bound, then one round16.  `out32` is the
+    value before that rounding: the kernel's fp16 lies between the fp16 roundings of the ends of out32's interval.
+  * dy_dx: per output dimension gd four fmas of w = (scale wd[o0]) wd[o1] times the corner difference, k = 0..3.  The
+    comment in grid_autograd.hip says the backward's dv uses the forward's accumulation order.  Checked against
+    grid_level: both start from w = scale, multiply by the o0 factor, then the o1 factor, take (1 - f) for a clear bit and
+    f for a set bit (grid_level writes the select, the backward indexes wd[d][bit] = {1 - f, f}), use the same cl / cr and
+    the same two fma chains from 0 -- the same fp32 operations on the same operands, so dv and dy_dx are bit-equal and one
+    function (_dv) restates both.
+  * dx, first order: a running sum over the 16 levels, in level order, of dy0 dv[d][0] + dy1 dv[d][1]; second order: per
+    level and pair (a, b) in the order (0,1), (0,2), (1,2), hab = dy0 h0 + dy1 h1 with h two fmas of
+    w = (scale scale) wd[t][k] (scale scale rounds once in fp32) times (v11 - v10) - (v01 - v00), then dx[a] += hab v[b],
+    dx[b] += hab v[a].  The bound is that chain's.
+  * ddy = (v0 dv[0] + v1 dv[1]) + v2 dv[2] per feature.
+  * Table gradient: per corner the record w dy s32 (first order: w = (wd0 wd1) wd2; second order:
+    w = ((v0 s0)(wd1 wd2) + (v1 s1)(wd0 wd2)) + (v2 s2)(wd0 wd1), s_d = +-scale by the corner's bit; s32 = gg_scale for an
+    fp32 table, 1 for an fp16 table, whose scatter applies the scale itself).  lvl_prereduce's runs (consecutive live lanes
+    of a 64-lane wave in the same cell; lanes with i >= n are off) are restated by neus_bwd_restatement._Table as
+    point_bwd uses it, with the three table terms of that module's docstring: the run's pre-reduction (6 u sum |records|),
+    then for fp32 atomics k u sum |run records|, for fp16 atomics each run record times gg_scale rounded to fp16 and k
+    read-modify-writes.  Entries that no record touches are exactly 0; a record whose two features are both exactly 0
+    issues no atomic, and a zero fp32 feature issues none (it is counted in k with value and bound 0).  The table result
+    is sparse: `idx` (entries some record reaches, ascending), and per such entry `value`, `bound`, `k`, `overflow`.
+  * fp16 table overflow: the fp16 mode overflows where |record gg_scale| or a partial sum passes 65504, as tiny-cuda-nn's
+    does.  `overflow` marks the entries whose sum of |records| (bounds included) reaches 65504 -- "may be non-finite" for
+    any order of the atomics; the tests choose upstream gradients for which it is empty and assert that it is.
+  * x outside [0, 1] is outside the contract: the reference clamps before the call, and (uint32_t)(int)floor wraps for
+    negative positions.  Not restated, not tested.
+
+_wrong (tests only) selects a deliberately wrong variant, which tests/test_grid_autograd_cpu.py requires to leave the
+bounds: 'skip_level_dx' (level 0 left out of dx), 'cross_sign' (the (0, 2) cross term negated at levels below 8),
+'wd_dim' (wd[a][k] in place of wd[t][k]), 'scale_once' (scale in place of scale scale at level 3), 's0_sign' (s0 negated
+in the directional corner weight), 'swap_features' (the two features of an entry exchanged in the table gradient),
+'first_lane' (a run's record taken from the run's first lane, which holds its own contribution only).
+"""
+import numpy as np
+
+import neus_bwd_restatement as R
+from neus_bwd_restatement import E, U16, add, cells, fma, grid_corners, mul, round16, sub
+from oracle import neus_oracle as NO
+
+LEVELS = R.LEVELS
+F16_MAX = 65504.0
+WRONG = ("skip_level_dx", "cross_sign", "wd_dim", "scale_once", "s0_sign", "swap_features", "first_lane")
+
+
+def _stack(xs, axis=-1):
+    return E(np.stack([x.v for x in xs], axis), np.stack([x.e for x in xs], axis))
+
+
+def _f32(x):
+    return float(np.float32(x))
+
+
+def _front(meta, l, x, grid16):
+    """cell, corner entries (global), wd[d][bit] = {1 - f, f} and the corner values of level l"""
+    scale = _f32(meta["scale"][l])
+    gi, f = cells(x, scale)
+    cidx = grid_corners(meta, l, gi) + int(meta["offset"][l])
+    fr = [E(f[:, d]) for d in range(3)]
+    wd = [[sub(1.0, fr[d]), fr[d]] for d in range(3)]
+    vals = None if grid16 is None else grid16.reshape(-1, 2)[cidx]          # [n,8,2] float64 (exact fp16 values)
+    return scale, gi, cidx, wd, vals
+
+
+def _dv(scale, wd, vals):
+    """d y_f / d x_gd of one level, dv[gd][f]: the order of grid_level and of the backward kernel (see the docstring)"""
+    n = vals.shape[0]
+    out = []
+    for gd in range(3):
+        o0, o1 = (1 if gd == 0 else 0), (1 if gd == 2 else 2)
+        a = [E(np.zeros(n)), E(np.zeros(n))]
+        for k in range(4):
+            w = mul(mul(scale, wd[o0][k & 1]), wd[o1][(k >> 1) & 1])
+            cl = ((k & 1) << o0) | (((k >> 1) & 1) << o1)
+            cr = cl | (1 << gd)
+            a = [fma(w, sub(vals[:, cr, ft], vals[:, cl, ft]), a[ft]) for ft in range(2)]
+        out.append(a)
+    return out
+
+
+def as_grid(grid16):
+    return np.asarray(grid16, np.float16).astype(np.float64).reshape(-1)
+
+
+def encode(x, grid16, meta=None):
+    """x f32 [n,3] in [0,1], grid16 f16 [total*2].  Returns {'out': E [n,32] (fp16), 'out32': E [n,32] (before the fp16
+    rounding), 'dy_dx': E [n,32,3]}."""
+    meta = meta or NO.grid_meta()
+    x = np.asarray(x, np.float32).reshape(-1, 3)
+    g = as_grid(grid16)
+    n = x.shape[0]
+    outs, dys = [], []
+    for l in range(LEVELS):
+        scale, _, _, wd, vals = _front(meta, l, x, g)
+        val = [E(np.zeros(n)), E(np.zeros(n))]
+        for c in range(8):
+            w = mul(mul(wd[0][c & 1], wd[1][(c >> 1) & 1]), wd[2][(c >> 2) & 1])
+            val = [fma(w, vals[:, c, ft], val[ft]) for ft in range(2)]
+        outs += val
+        dv = _dv(scale, wd, vals)
+        dys += [_stack([dv[gd][ft] for gd in range(3)]) for ft in range(2)]
+    out32 = _stack(outs)
+    return {"out": round16(out32), "out32": out32, "dy_dx": _stack(dys, 1)}
+
+
+def _sparse(tab):
+    """neus_bwd_restatement._Table.result() on the entries some record reaches only (the dense table has 12.6 M)"""
+    idx = np.nonzero(tab.touched)[0]
+    c = object.__new__(R._Table)
+    c.mode = tab.mode
+    for k in ("S", "Eb", "A", "K", "A_at", "hashed", "touched"):
+        setattr(c, k, getattr(tab, k)[idx])
+    S, B = c.result()
+    over = (c.A * (1 + 2 * U16) >= F16_MAX) if tab.mode != "f32" else np.zeros(idx.size, bool)
+    return {"idx": idx, "value": S, "bound": B, "k": c.K, "overflow": over}
+
+
+def backward(x, grid16, dy, dy_scale=1.0, v=None, table_mode="f32", gg_scale=1.0, meta=None, tables=None, _wrong=None):
+    """x f32 [n,3] in [0,1]; grid16 f16 [total*2] or None (table gradient only); dy [n,32] f32 or f16 (the kernel reads
+    dy * dy_scale); v f32 [n,3] or None (first order).  Returns {'dx': E [n,3], 'ddy': E [n,32] (second order only),
+    'table': sparse result (see the docstring) in the kernel's units (x gg_scale)}.  tables: a list of
+    (table_mode, gg_scale) evaluated from one pass; the result then has 'tables': {(mode, scale): sparse result} too."""
+    assert _wrong is None or _wrong in WRONG
+    meta = meta or NO.grid_meta()
+    x = np.asarray(x, np.float32).reshape(-1, 3)
+    n = x.shape[0]
+    g = None if grid16 is None else as_grid(grid16)
+    dy = np.asarray(dy)
+    assert dy.dtype in (np.float16, np.float32) and dy.shape == (n, 32)
+    dys = _f32(dy_scale)
+    dyl = E(dy.astype(np.float64)) if dys == 1.0 else mul(dy.astype(np.float64), dys)
+    second = v is not None
+    vv = [E(np.asarray(v, np.float32).astype(np.float64)[:, d]) for d in range(3)] if second else None
+    modes = list(tables) if tables is not None else [(table_mode, gg_scale)]
+    on = np.ones(n, bool)
+    tabs = {m: R._Table(m[0], meta, on, m[1] if m[0] != "f32" else 1.0) for m in modes}
+    dxa = [E(np.zeros(n)) for _ in range(3)]
+    ddy = []
+    for l in range(LEVELS):
+        scale, gi, cidx, wd, vals = _front(meta, l, x, g)
+        dl = [dyl[:, 2 * l], dyl[:, 2 * l + 1]]
+        # a level whose upstream features are all exactly 0 (one-hot upstreams): every record is an exact 0 (no atomic)
+        # and its dx terms are exact zeros, whose addition is exact -- nothing to restate but ddy
+        idle = not (dl[0].v.any() or dl[1].v.any())
+        # ---- table records
+        rec = []
+        for c in ([] if idle else range(8)):
+            b = [(c >> d) & 1 for d in range(3)]
+            if not second:
+                w = mul(mul(wd[0][b[0]], wd[1][b[1]]), wd[2][b[2]])
+            else:
+                s = [scale if b[d] else -scale for d in range(3)]
+                if _wrong == "s0_sign":
+                    s[0] = -s[0]
+                w = add(add(mul(mul(vv[0], s[0]), mul(wd[1][b[1]], wd[2][b[2]])),
+                            mul(mul(vv[1], s[1]), mul(wd[0][b[0]], wd[2][b[2]]))),
+                        mul(mul(vv[2], s[2]), mul(wd[0][b[0]], wd[1][b[1]])))
+            rec.append(_stack([mul(w, dl[0]), mul(w, dl[1])]))
+        G = None if idle else _stack(rec, 1)                                # [n,8,2]
+        for m, tab in ([] if idle else tabs.items()):
+            Gm = G
+            if m[0] == "f32" and _f32(m[1]) != 1.0:
+                Gm = mul(G, _f32(m[1]))
+            if _wrong == "swap_features":
+                Gm = E(Gm.v[..., ::-1], Gm.e[..., ::-1])
+            if _wrong == "first_lane":
+                run = tab.runs(gi)
+                first = np.concatenate([[True], run[1:] != run[:-1]])
+                Gm = R.live(Gm, first[:, None, None])
+            tab.add_level(l, gi, cidx, Gm)
+        if g is None:
+            continue
+        # ---- values
+        if idle and not second:
+            continue
+        dv = _dv(scale, wd, vals)
+        if not second:
+            for d in range(3):
+                dxa[d] = add(dxa[d], add(mul(dl[0], dv[d][0]), mul(dl[1], dv[d][1])))
+            continue
+        for ft in range(2):
+            ddy.append(add(add(mul(vv[0], dv[0][ft]), mul(vv[1], dv[1][ft])), mul(vv[2], dv[2][ft])))
+        if idle or (_wrong == "skip_level_dx" and l == 0):
+            continue
+        s2 = mul(scale, scale)
+        if _wrong == "scale_once" and l == 3:
+            s2 = E(scale)
+        for a in range(3):
+            for b in range(a + 1, 3):
+                t = 3 - a - b
+                h = [E(np.zeros(n)), E(np.zeros(n))]
+                for k in range(2):
+                    base = k << t
+                    c11, c10, c01, c00 = base | (1 << a) | (1 << b), base | (1 << a), base | (1 << b), base
+                    w = mul(s2, wd[a if _wrong == "wd_dim" else t][k])
+                    h = [fma(w, sub(sub(vals[:, c11, ft], vals[:, c10, ft]), sub(vals[:, c01, ft], vals[:, c00, ft])),
+                             h[ft]) for ft in range(2)]
+                hab = add(mul(dl[0], h[0]), mul(dl[1], h[1]))
+                if _wrong == "cross_sign" and (a, b) == (0, 2) and l < 8:
+                    hab = E(-hab.v, hab.e)
+                dxa[a] = add(dxa[a], mul(hab, vv[b]))
+                dxa[b] = add(dxa[b], mul(hab, vv[a]))
+    res = {m: _sparse(t) for m, t in tabs.items()}
+    out = {"table": res[modes[0]], "tables": res}
+    if g is not None:
+        out["dx"] = _stack(dxa)
+        if second:
+            out["ddy"] = _stack(ddy)
+    return out
+
+
+def level_slice(meta, l):
+    """[a, b) of level l in the flat table (2 features per entry)"""
+    a = 2 * int(meta["offset"][l])
+    return a, a + 2 * int(meta["size"][l])
+
+
+def dense(tab, meta):
+    """(value, bound, k) of a sparse table result as dense arrays [total*2]"""
+    tot = int(meta["total"]) * 2
+    out = []
+    for key in ("value", "bound", "k"):
+        a = np.zeros(tot)
+        a[tab["idx"]] = tab[key]
+        out.append(a)
+    return tuple(out)
+
+
+# ------------------------------------------------------------------------------------------------------ scenes ----
+SCENES = ("uniform", "clump", "ray", "faces", "corners", "one")
+FACE_LEVELS = (0, 1, 4, 7, 15)
+RAY_SAMPLES = 72
+
+
+def face_coordinate(l, meta, target):
+    """a coordinate in [0, 1] near `target` with f == 0 exactly at level l: the search of
+    neus_bwd_restatement._face_value, in the encoding's own coordinate (that one walks world coordinates through the
+    bound normalisation, which does not reach every face of the finest level)"""
+    sc = _f32(meta["scale"][l])
+    k0 = int(np.floor(float(target) * sc + 0.5))
+    for k in sorted(range(max(1, k0 - 8), k0 + 8), key=lambda k: abs(k - k0)):
+        c = np.float32((k - 0.5) / sc)
+        cand = [c]
+        lo = hi = c
+        for _ in range(16):
+            lo, hi = np.nextafter(lo, np.float32(-9)), np.nextafter(hi, np.float32(9))
+            cand += [lo, hi]
+        xs = np.array(cand, np.float32)
+        _, f = cells(np.stack([xs, xs, xs], 1), sc)
+        hit = np.nonzero((f[:, 0] == 0.0) & (xs > 0) & (xs < 1))[0]
+        if hit.size:
+            return xs[hit[0]]
+    raise AssertionError("no face point found")
+
+
+def scene(name, n, seed=1, meta=None):
+    """x f32 [n,3] in [0,1]:
+      uniform   uniform random
+      clump     the first quarter of the points inside a few coarse cells: long merged runs
+      ray       consecutive points along lines, 72 per line (the product's layout; 72 does not divide 64, so runs cross the
+                wave boundaries at lanes 63 / 64), clipped to the box
+      faces     components with f == 0 exactly at levels 0, 1, 4, 7, 15 (one component at a time, then all three)
+      corners   components exactly 0 and exactly 1 (all eight corners of the box, then one or two components); x = 1 takes
+                a dense level's corner index past the level's size
+      one       a single point (n is ignored)"""
+    meta = meta or NO.grid_meta()
+    rng = np.random.default_rng(seed)
+    if name == "one":
+        return rng.random((1, 3)).astype(np.float32)
+    x = rng.random((n, 3))
+    if name == "uniform":
+        pass
+    elif name == "clump":
+        q = max(n // 4, 1)
+        x[:q] = x[:q] * 0.02 + 0.4
+    elif name == "ray":
+        nr = -(-n // RAY_SAMPLES)
+        o = rng.uniform(0.1, 0.9, (nr, 3))
+        d = rng.standard_normal((nr, 3))
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+        t = np.arange(RAY_SAMPLES) * (0.25 / RAY_SAMPLES)
+        x = np.clip(o[:, None] + d[:, None] * t[None, :, None], 0.0, 1.0).reshape(-1, 3)[:n]
+    elif name == "faces":
+        row = 0
+        for l in FACE_LEVELS:
+            for d in range(4):
+                if row < n:
+                    for dd in (range(3) if d == 3 else (d,)):
+                        x[row, dd] = face_coordinate(l, meta, x[row, dd])
+                row += 1
+    elif name == "corners":
+        row = 0
+        for c in range(8):
+            if row < n:
+                x[row] = [(c >> d) & 1 for d in range(3)]
+            row += 1
+        for d in range(3):
+            for val in (0.0, 1.0):
+                if row < n:
+                    x[row, d] = val
+                if row + 1 < n:
+                    x[row + 1, d], x[row + 1, (d + 1) % 3] = val, 1.0 - val
+                row += 2
+        if n > 40:                                  # a run of lanes in the far corner cell, and a scatter of 0 / 1
+            x[32:40] = 1.0
+            pick = rng.random((n - 40, 3))
+            x[40:] = np.where(pick < 0.1, 0.0, np.where(pick > 0.9, 1.0, x[40:]))
+    else:
+        raise KeyError(name)
+    return x.astype(np.float32)
+
+
+def table(kind, seed=0, meta=None):
+    """grid f16 [total*2]: 'flat' U(-0.3, 0.3) (well-conditioned corner differences), 'init' tcnn's initial U(-1e-4, 1e-4)
+    (few significant fp16 bits, second differences that cancel)"""
+    meta = meta or NO.grid_meta()
+    rng = np.random.default_rng(seed)
+    amp = {"flat": 0.3, "init": 1e-4}[kind]
+    return ((rng.random(int(meta["total"]) * 2, np.float32) * 2 - 1) * np.float32(amp)).astype(np.float16)
+
+
+DY_AMP = 0.05       # upstream of the value path (the existing drop-in test's fp16-mode amplitudes)
+V_AMP = 1e-3        # upstream of the gradient path
+
+
+# (dy dtype, dy_scale, one-hot level, v) of the dense upstreams the GPU test runs; its one-hot-per-level upstreams are
+# these with all but one level's features zeroed, so their records are a subset
+UPSTREAMS = (("f32", 1.0, None, "dense"), ("f16", 1.0, None, "dense"), ("f32", 1.0 / 128, None, "dense"),
+             ("f16", 1.0 / 128, None, 0), ("f32", 1.0, None, 1), ("f16", 1.0, None, 2))
+
+
+def upstream(n, seed, dtype="f32", dy_scale=1.0, level=None, v="dense"):
+    """(dy [n,32] in `dtype` holding gradient / dy_scale, v f32 [n,3]).  level: only that level's two features non-zero;
+    v: 'dense', or an axis 0..2 (v along that axis only)."""
+    rng = np.random.default_rng(seed)
+    d = rng.standard_normal((n, 32)) * DY_AMP
+    if level is not None:
+        keep = np.zeros(32, bool)
+        keep[2 * level:2 * level + 2] = True
+        d = d * keep
+    d = (d / dy_scale).astype(np.float16 if dtype == "f16" else np.float32)
+    vv = rng.standard_normal((n, 3)) * V_AMP
+    if v != "dense":
+        keep = np.zeros(3, bool)
+        keep[int(v)] = True
+        vv = vv * keep
+    return d, vv.astype(np.float32)

@@ -101,6 +101,86 @@ def test_encoding_autograd_first_and_second_order(T, O, dev, grad_dtype):
            "x": _rel(xg.grad.cpu(), xo.grad)}
     assert rep["grid"] < 5e-3 and rep["c"] < 5e-3 and rep["x"] < 5e-3, rep
 
+    # ---- per level: a first derivative carries the level's scale (15 .. 4095) and a mixed second derivative its
+    # square, so the fine levels own the norms above and a coarse level could be wrong or missing under them
+    meas = _LEVEL_REL["f16" if grad_dtype == torch.float16 else "f32"]
+    ref = _level_oracle(NA, meta, grid, x, A, c, B)
+    pg = enc_m.params.grad.double().cpu()
+    bad = {}
+    for l in range(16):
+        a, b = 2 * int(meta["offset"][l]), 2 * (int(meta["offset"][l]) + int(meta["size"][l]))
+        r = _rel(pg[a:b], ref["grid"][a:b])
+        if not r < 2 * meas["grid"][l]:
+            bad[f"grid[{l}]"] = (r, 2 * meas["grid"][l])
+    # one backward per one-hot level: A and c masked to level l's two features
+    for l in range(16):
+        m = torch.zeros(32)
+        m[2 * l:2 * l + 2] = 1.0
+        enc_m.params.grad = None
+        xl = x.to(dev).requires_grad_(True)
+        cl = (c * m).to(dev).requires_grad_(True)
+        with torch.enable_grad():
+            yl = enc_m(xl)
+            sl = (yl.float() * cl).sum(-1, keepdim=True)
+            gl = torch.autograd.grad(outputs=sl, inputs=xl, grad_outputs=torch.ones_like(sl), create_graph=True,
+                                     retain_graph=True, only_inputs=True)[0]
+        ((yl.float() * (A * m).to(dev)).sum() + (gl * B.to(dev)).sum()).backward()
+        rx = _rel(xl.grad.double().cpu(), ref["x"][l])
+        rc = _rel(cl.grad.double().cpu()[2 * l:2 * l + 2], ref["c"][2 * l:2 * l + 2])
+        if not rx < 2 * meas["x"][l]:
+            bad[f"x[{l}]"] = (rx, 2 * meas["x"][l])
+        if not rc < 2 * meas["c"][l]:
+            bad[f"c[{l}]"] = (rc, 2 * meas["c"][l])
+    assert not bad, bad
+
+
+# Per-level relative L2 error against the float64 oracle that a correct fp32 / fp16 kernel can reach in the test above:
+# measured on the CPU as _rel between the float64 autograd oracle and tests/grid_autograd_restatement.py evaluated at its
+# bound (every element value +- bound, away from the oracle), on this test's inputs (the kernel reads fp16(A) and fp16(c)
+# as the upstream; `grid`: the sum of the first- and second-order table gradients, in the fp16 mode each through fp16
+# atomics under the loss scale, whose bound grows with the number of records an entry takes -- the clump puts hundreds
+# into a few entries of levels 2 .. 5; `c`: d L / d dy rounded to fp16 per element, as the drop-in returns it in dy's dtype,
+# then summed over the points in fp32).  The test allows twice these (a factor 2 for the atomics' order).
+_LEVEL_REL = {
+    "f32": {
+        "grid": (1.31e-05, 6.42e-06, 3.98e-05, 4.48e-05, 3.28e-05, 1.84e-05, 7.82e-06, 4.37e-06, 1.66e-06, 1.13e-06,
+                 9.89e-07, 9.65e-07, 9.64e-07, 1.04e-06, 9.11e-07, 9.05e-07),
+        "x": (1.32e-05, 3.40e-06, 5.15e-06, 3.79e-06, 2.15e-06, 1.57e-06, 1.26e-06, 3.47e-06, 1.18e-06, 1.07e-06,
+              9.31e-07, 1.06e-06, 1.07e-06, 1.17e-06, 8.91e-07, 9.82e-07),
+        "c": (6.78e-03, 1.09e-02, 6.81e-03, 8.85e-03, 8.55e-03, 8.97e-03, 1.03e-02, 1.21e-02, 8.58e-03, 1.05e-02,
+              1.27e-02, 2.06e-02, 6.91e-03, 7.81e-03, 3.02e-02, 2.03e-02)},
+    "f16": {
+        "grid": (3.56e-03, 2.94e-03, 4.19e-01, 4.53e-01, 2.91e-01, 1.43e-01, 5.11e-02, 1.51e-02, 4.53e-03, 1.87e-03,
+                 1.22e-03, 1.06e-03, 1.03e-03, 1.03e-03, 1.01e-03, 9.91e-04),
+        "x": (1.93e-04, 1.19e-04, 1.61e-04, 1.28e-04, 6.30e-05, 4.14e-05, 2.52e-05, 1.25e-04, 2.30e-05, 6.71e-06,
+              6.05e-06, 6.88e-06, 7.46e-06, 1.27e-05, 2.08e-06, 1.68e-06),
+        "c": (6.92e-03, 1.10e-02, 6.87e-03, 8.90e-03, 8.58e-03, 8.99e-03, 1.03e-02, 1.21e-02, 8.59e-03, 1.05e-02,
+              1.27e-02, 2.06e-02, 6.91e-03, 7.81e-03, 3.02e-02, 2.03e-02)},
+}
+
+
+def _level_oracle(NA, meta, grid, x, A, c, B):
+    """the oracle of the test above in float64: the table gradient (split by level by the caller), d L / d c, and
+    d L / d x of each one-hot level (A and c masked to the level's two features)"""
+    old = torch.get_default_dtype()
+    torch.set_default_dtype(torch.float64)
+    try:
+        go = grid.double().requires_grad_(True)
+        xo = x.double().requires_grad_(True)
+        co = c.double().requires_grad_(True)
+        enc_o, dydx_o = NA.grid_encode_diff(xo, go, meta, x_differentiable=True)
+        c16 = NA._ste_half(co)
+        loss = lambda m: (enc_o * (A.double() * m)).sum() + (torch.einsum("ncd,c->nd", dydx_o, c16 * m) * B.double()).sum()
+        gg, gc = torch.autograd.grad(loss(torch.ones(32)), [go, co], retain_graph=True)
+        gx = []
+        for l in range(16):
+            m = torch.zeros(32)
+            m[2 * l:2 * l + 2] = 1.0
+            gx.append(torch.autograd.grad(loss(m), xo, retain_graph=True)[0])
+        return {"grid": gg, "c": gc, "x": gx}
+    finally:
+        torch.set_default_dtype(old)
+
 
 def test_encoding_backward_without_create_graph_and_no_grad_path(T, O, dev):
     """Plain first-order use (loss.backward() only) and torch.no_grad() inference."""
