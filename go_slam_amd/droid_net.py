@@ -14,6 +14,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .weight_packs import WeightPacks, conv_pack, tensors_key
+
 
 class GradientClip(nn.Module):
     """Forward identity (the reference clips gradients in backward only, modules/clipping.py)."""
@@ -94,15 +96,11 @@ def pack_1x1_weight(weight):
 def conv1x1_bias_act(cache, conv, x, act):
     """act(conv1x1(x) + bias) for NHWC fp16 x in one HIP launch (gs_conv1x1)."""
     from . import _lib
-    key = (conv.weight._version, conv.bias._version, conv.weight.device, conv.weight.data_ptr())
-    hit = cache.get(id(conv))
-    if hit is None or hit[0] != key:
-        hit = (key, pack_1x1_weight(conv.weight), conv.bias.detach().float().contiguous())
-        cache[id(conv)] = hit
+    wpack, bias = conv_pack(cache, conv, "1x1", pack_1x1_weight)
     n, K, h, w = x.shape
     N = conv.weight.shape[0]
     y = torch.empty((n, N, h, w), dtype=torch.float16, device=x.device, memory_format=torch.channels_last)
-    rc = _lib.lib().gs_conv1x1(_lib.ptr(x), K, K, _lib.ptr(hit[1]), _lib.ptr(hit[2]), _ACT[act], _lib.ptr(y), N, N,
+    rc = _lib.lib().gs_conv1x1(_lib.ptr(x), K, K, _lib.ptr(wpack), _lib.ptr(bias), _ACT[act], _lib.ptr(y), N, N,
                                n * h * w, _lib.stream_ptr(x.device))
     _lib.check(rc, "conv1x1")
     return y
@@ -128,15 +126,11 @@ def conv7x7_c4_supported(conv, x):
 def conv7x7_c4_bias_act(cache, conv, x, act, rt=0):
     """act(conv7x7(x) + bias) for a 4-channel NHWC fp16 x in one HIP launch (gs_conv7x7_c4); act: none / relu."""
     from . import _lib
-    key = (conv.weight._version, conv.bias._version, conv.weight.device, conv.weight.data_ptr())
-    hit = cache.get(id(conv))
-    if hit is None or hit[0] != key:
-        hit = (key, pack_conv7x7_c4_weight(conv.weight), conv.bias.detach().float().contiguous())
-        cache[id(conv)] = hit
+    wpack, bias = conv_pack(cache, conv, "7x7", pack_conv7x7_c4_weight)
     n, _, h, w = x.shape
     y = torch.empty((n, 128, h, w), dtype=torch.float16, device=x.device, memory_format=torch.channels_last)
     with torch.cuda.device(x.device):
-        rc = _lib.lib().gs_conv7x7_c4(_lib.ptr(x), _lib.ptr(hit[1]), _lib.ptr(hit[2]), _lib.ptr(y), 128, n, h, w,
+        rc = _lib.lib().gs_conv7x7_c4(_lib.ptr(x), _lib.ptr(wpack), _lib.ptr(bias), _lib.ptr(y), 128, n, h, w,
                                       int(act == "relu"), int(rt), _lib.stream_ptr(x.device))
     _lib.check(rc, "conv7x7_c4")
     return y
@@ -146,17 +140,13 @@ def conv3x3_head(x, conv, cache, epilogue="none", out_scale=1.0, in_channel=0, i
     """epi(conv(relu?(x[:, in_channel:in_channel+128] + in_bias)) + bias) * out_scale -> fp32 [n,h,w,O]
     (values are the reference's fp16 results), one HIP launch (gs_conv3x3_head)."""
     from . import _lib
-    key = (conv.weight._version, conv.bias._version, conv.weight.device, conv.weight.data_ptr())
-    hit = cache.get(id(conv))
-    if hit is None or hit[0] != key:
-        hit = (key, pack_head_weight(conv.weight), conv.bias.detach().float().contiguous())
-        cache[id(conv)] = hit
+    wpack, bias = conv_pack(cache, conv, "head", pack_head_weight)
     n, C, h, w = x.shape
     O = conv.weight.shape[0]
     out = torch.empty(n, h, w, O, dtype=torch.float32, device=x.device)
     epi = {"none": 0, "sigmoid": 1, "softplus": 2}[epilogue]
     rc = _lib.lib().gs_conv3x3_head(x.data_ptr() + 2 * in_channel, C, _lib.ptr(in_bias), int(in_relu),
-                                    _lib.ptr(hit[1]), _lib.ptr(hit[2]), O, epi, float(out_scale), _lib.ptr(out),
+                                    _lib.ptr(wpack), _lib.ptr(bias), O, epi, float(out_scale), _lib.ptr(out),
                                     n, h, w, _lib.stream_ptr(x.device))
     _lib.check(rc, "conv3x3_head")
     return out
@@ -172,24 +162,7 @@ def cvx_upsample(data, mask):
     return up.permute(0, 4, 2, 5, 3, 1).reshape(b, 8 * h, 8 * w, d)
 
 
-class _HalfWeights:
-    """fp16 / NHWC copies of conv weights (+ fp32 biases) for the inference fast path, refreshed when
-    the parameters change (load_state_dict, .to, optimiser steps bump `_version`)."""
-
-    def __init__(self):
-        self._cache = {}
-
-    def get(self, conv):
-        key = (conv.weight._version, conv.bias._version, conv.weight.device, conv.weight.data_ptr())
-        hit = self._cache.get(id(conv))
-        if hit is None or hit[0] != key:
-            w = conv.weight.detach().half().contiguous(memory_format=torch.channels_last)
-            b = conv.bias.detach().float().contiguous()
-            hit = (key, w, b)
-            self._cache[id(conv)] = hit
-        return hit[1], hit[2]
-
-
+_HalfWeights = WeightPacks      # the name conv_bias_act's callers construct its cache by
 _ACT = {"none": 0, "relu": 1, "sigmoid": 2}
 
 
@@ -299,8 +272,9 @@ def conv_nobias(x, w, stride=1, padding=0):
 def conv_bias_act(cache, conv, x, act, out=None, out_channel=0):
     """act(conv(x) + bias) for NHWC fp16 x: bias-free convolution (gs_conv3x3 or MIOpen) + one fused HIP epilogue
     (PyTorch issues conv, add_(bias) and relu_ as three passes).  With `out` (an NHWC fp16 tensor
-    with more channels) the result lands in out[:, out_channel:out_channel+C] -- no torch.cat."""
-    w, b = cache.get(conv)
+    with more channels) the result lands in out[:, out_channel:out_channel+C] -- no torch.cat.  `cache`: a WeightPacks
+    (the fp16 NHWC weight and the fp32 bias are cast once per weight version)."""
+    w, b = conv_pack(cache, conv, "nhwc", lambda t: t.detach().half().contiguous(memory_format=torch.channels_last))
     if GRU_FUSED_EPILOGUE and act == "relu" and _use_own_conv3x3(x, w, conv.stride, conv.padding):
         from . import _lib
         n, c, h, wd = x.shape
@@ -340,23 +314,18 @@ class LazyUpmask:
     def materialize(self):
         if self._value is None:
             m = self.module
-            self._value = conv1x1_bias_act(m._head_cache, m.agg.upmask[0], self.x, "none").view(*self.shape_)
+            self._value = conv1x1_bias_act(m._packs, m.agg.upmask[0], self.x, "none").view(*self.shape_)
         return self._value
 
     def upsample_into(self, disps, ix, disps_up):
         from . import _lib
-        conv = self.module.agg.upmask[0]
-        cache = self.module._head_cache
-        key = (conv.weight._version, conv.bias._version, conv.weight.device, conv.weight.data_ptr())
-        hit = cache.get("upmask_plain")
-        if hit is None or hit[0] != key:
-            hit = (key, conv.weight.detach().reshape(576, 128).half().contiguous(), conv.bias.detach().float().contiguous())
-            cache["upmask_plain"] = hit
+        wplain, bias = conv_pack(self.module._packs, self.module.agg.upmask[0], "plain",
+                                 lambda w: w.detach().reshape(576, 128).half().contiguous())
         x = self.x
         m, c, h, w = x.shape
         assert c == 128 and x.is_contiguous(memory_format=torch.channels_last) and ix.numel() == m
         with torch.cuda.device(x.device):
-            rc = _lib.lib().gs_upmask_upsample(_lib.ptr(x), 128, _lib.ptr(hit[1]), _lib.ptr(hit[2]), _lib.ptr(disps),
+            rc = _lib.lib().gs_upmask_upsample(_lib.ptr(x), 128, _lib.ptr(wplain), _lib.ptr(bias), _lib.ptr(disps),
                                                _lib.ptr(ix), _lib.ptr(disps_up), m, h, w, _lib.stream_ptr(x.device))
         _lib.check(rc, "upmask_upsample")
 
@@ -379,18 +348,24 @@ class ConvGRU(nn.Module):
         self.convz_glo = nn.Conv2d(h_planes, h_planes, 1)
         self.convr_glo = nn.Conv2d(h_planes, h_planes, 1)
         self.convq_glo = nn.Conv2d(h_planes, h_planes, 1)
+        self._packs = WeightPacks()
 
     def _fusable(self, net, inputs):
         cl = torch.channels_last
         return (net.is_cuda and not torch.is_grad_enabled() and net.dtype == torch.float16 and net.shape[1] == 128
                 and net.is_contiguous(memory_format=cl) and all(t.dtype == torch.float16 for t in inputs))
 
-    def _half_weights(self):
-        """fp16 NHWC copies of the conv weights (convz|convr fused to one 448->256 conv), cached."""
+    def _weight_tensors(self):
         mods = (self.convz, self.convr, self.convq, self.w, self.convz_glo, self.convr_glo, self.convq_glo)
-        key = tuple(m.weight._version for m in mods) + tuple(m.bias._version for m in mods) + \
-            (self.convz.weight.device, self.convz.weight.data_ptr())
-        if getattr(self, "_hw_key", None) != key:
+        return [m.weight for m in mods] + [m.bias for m in mods]
+
+    def _weights_key(self):
+        """changes when any of the weights does (UpdateModule drops its hoisted context terms then)"""
+        return tensors_key(self._weight_tensors())
+
+    def _all_packs(self):
+        """(_half_weights(), _hw_hoist, _ww_pack), cached"""
+        def build():
             cl = torch.channels_last
             wzr = torch.cat([self.convz.weight, self.convr.weight], 0).detach().half().contiguous(memory_format=cl)
             wq = self.convq.weight.detach().half().contiguous(memory_format=cl)
@@ -406,12 +381,18 @@ class ConvGRU(nn.Module):
             # part over [net | corr | flow] (320 input channels, run every update)
             keep = list(range(0, 128)) + list(range(256, self.convz.weight.shape[1]))
             w_all = torch.cat([self.convz.weight, self.convr.weight, self.convq.weight], 0).detach()
-            self._hw_hoist = (w_all[:, 128:256].half().contiguous(memory_format=cl),
-                              w_all[:256][:, keep].half().contiguous(memory_format=cl),
-                              w_all[256:][:, keep].half().contiguous(memory_format=cl))
-            self._ww_pack = pack_1x1_weight(self.w.weight)
-            self._hw, self._hw_key = (wzr, wq, bzr, bq, ww, bw, glo), key
-        return self._hw
+            hoist = (w_all[:, 128:256].half().contiguous(memory_format=cl),
+                     w_all[:256][:, keep].half().contiguous(memory_format=cl),
+                     w_all[256:][:, keep].half().contiguous(memory_format=cl))
+            return (wzr, wq, bzr, bq, ww, bw, glo), hoist, pack_1x1_weight(self.w.weight)
+        return self._packs.get("gru", self._weight_tensors(), build)
+
+    def _half_weights(self):
+        """fp16 NHWC copies of the conv weights (convz|convr fused to one 448->256 conv)"""
+        return self._all_packs()[0]
+
+    _hw_hoist = property(lambda self: self._all_packs()[1])     # (W_inp, W_zr rest, W_q rest) of the hoisted form
+    _ww_pack = property(lambda self: self._all_packs()[2])      # gs_conv1x1 fragments of `w`
 
     def _forward_fused(self, net, inputs):
         """Same mathematics as forward(); the 3x3 convolutions go through conv_nobias, everything between them is
@@ -426,7 +407,6 @@ class ConvGRU(nn.Module):
         By linearity conv(W, [net|inp|corr|flow]) = conv(W_inp, inp) + conv(W_rest, [net|corr|flow]); inp
         is constant while an edge lives, so this term is computed once per edge set instead of in
         every update (2 x 28.6 % of the GRU's convolution FLOPs)."""
-        self._half_weights()
         return conv_nobias(inp, self._hw_hoist[0], padding=1)
 
     def global_context(self, net):
@@ -434,7 +414,7 @@ class ConvGRU(nn.Module):
         from . import _lib
         b, c, h, w = net.shape
         hw = h * w
-        wzr, wq, bzr, bq, ww, bw, gw = self._half_weights()
+        (wzr, wq, bzr, bq, ww, bw, gw), _, ww_pack = self._all_packs()
         L = _lib.lib()
         st = _lib.stream_ptr(net.device)
         dev = net.device
@@ -443,7 +423,7 @@ class ConvGRU(nn.Module):
         if GRU_GLO_FUSED:
             # w(net), sigmoid, * net and the pooling in one kernel: w_pre never reaches memory
             ws = torch.empty(L.gs_gru_glo_fused_workspace_bytes(b, hw), dtype=torch.uint8, device=dev)
-            _lib.check(L.gs_gru_glo_fused(_lib.ptr(net), 128, _lib.ptr(self._ww_pack), _lib.ptr(bw), _lib.ptr(gw[0]),
+            _lib.check(L.gs_gru_glo_fused(_lib.ptr(net), 128, _lib.ptr(ww_pack), _lib.ptr(bw), _lib.ptr(gw[0]),
                                           _lib.ptr(gw[1]), _lib.ptr(gw[2]), _lib.ptr(gw[3]), _lib.ptr(gw[4]),
                                           _lib.ptr(gw[5]), _lib.ptr(gzr), _lib.ptr(gq), b, hw, _lib.ptr(ws),
                                           ws.numel(), st), "gru_glo_fused")
@@ -451,7 +431,7 @@ class ConvGRU(nn.Module):
             # gs_conv1x1 (own MFMA kernel; deterministic, one launch) instead of an MIOpen 1x1 convolution, whose
             # solver choice -- and with it the fp16 rounding of the global-context gate -- can change between calls
             w_pre = torch.empty_like(net)
-            _lib.check(L.gs_conv1x1(_lib.ptr(net), 128, 128, _lib.ptr(self._ww_pack), None, 0, _lib.ptr(w_pre), 128,
+            _lib.check(L.gs_conv1x1(_lib.ptr(net), 128, 128, _lib.ptr(ww_pack), None, 0, _lib.ptr(w_pre), 128,
                                     128, b * hw, st), "conv1x1(gru.w)")
             ws = torch.empty(L.gs_gru_glo_workspace_bytes(b), dtype=torch.uint8, device=dev)
             _lib.check(L.gs_gru_glo(_lib.ptr(w_pre), _lib.ptr(bw), _lib.ptr(net), _lib.ptr(gw[0]), _lib.ptr(gw[1]),
@@ -466,9 +446,9 @@ class ConvGRU(nn.Module):
         from . import _lib
         b, c, h, w = net.shape
         hw = h * w
-        wzr, wq, bzr, bq, ww, bw, gw = self._half_weights()
+        (wzr, wq, bzr, bq, ww, bw, gw), hoist, _ = self._all_packs()
         if inp_pre is not None:
-            wzr, wq = self._hw_hoist[1], self._hw_hoist[2]
+            wzr, wq = hoist[1], hoist[2]
         L = _lib.lib()
         st = _lib.stream_ptr(net.device)
         dev = net.device
@@ -558,8 +538,7 @@ class UpdateModule(nn.Module):
         self.gru = ConvGRU(128, 128 + 128 + 64)
         self.agg = GraphAgg()
         self.fuse_epilogues = True      # inference fast path: bias-free convs + fused HIP epilogues
-        self._hw = _HalfWeights()
-        self._head_cache = {}
+        self._packs = WeightPacks()
 
     def drop_edge_caches(self):
         """Forget what is cached per edge set (the hoisted context-feature convolutions).  Happens by itself when `inp`
@@ -631,8 +610,7 @@ class UpdateModule(nn.Module):
         cache = getattr(self, "_inp_pre_cache", None)
         if cache is None:
             cache = self._inp_pre_cache = collections.OrderedDict()
-        self.gru._half_weights()                              # refreshes gru._hw_key if the weights changed
-        wkey = self.gru._hw_key
+        wkey = self.gru._weights_key()
         # keyed by the MEMORY the features live in (address, shape, strides, dtype) and validated by the tensor's version
         # counter, which views share: `self.inp[None]` is a new Python object on every call (MotionFilter.track, 35 us per
         # input frame of recomputation with an object-identity key).
@@ -678,23 +656,21 @@ class UpdateModule(nn.Module):
     def _head_weights(self):
         """delta[0] | weight[0] | agg.conv1 read the same tensor: one 128->384 convolution."""
         mods = (self.delta[0], self.weight[0], self.agg.conv1)
-        key = tuple(m.weight._version for m in mods) + tuple(m.bias._version for m in mods) + \
-            (mods[0].weight.device, mods[0].weight.data_ptr())
-        if getattr(self, "_heads_key", None) != key:
+
+        def build():
             w = torch.cat([m.weight for m in mods], 0).detach().half().contiguous(memory_format=torch.channels_last)
-            b = [m.bias.detach().float().contiguous() for m in mods]
-            self._heads, self._heads_key = (w, b), key
-        return self._heads
+            return w, [m.bias.detach().float().contiguous() for m in mods]
+        return self._packs.get("heads", [m.weight for m in mods] + [m.bias for m in mods], build)
 
     def _corr_independent_part(self, net4, inp, f4, n, ht, wd):
         """everything of the fast path that does not need the correlation features: the GRU input buffer with net and the
         flow-encoder features in place, the hoisted context term, the GRU's global-context terms"""
         hx, inp_pre = self._edge_state(inp, n, ht, wd)
         if CONV7X7_OWN and conv7x7_c4_supported(self.flow_encoder[0], f4):
-            f4 = conv7x7_c4_bias_act(self._head_cache, self.flow_encoder[0], f4, "relu")
+            f4 = conv7x7_c4_bias_act(self._packs, self.flow_encoder[0], f4, "relu")
         else:
-            f4 = conv_bias_act(self._hw, self.flow_encoder[0], f4, "relu")
-        conv_bias_act(self._hw, self.flow_encoder[2], f4, "relu", out=hx, out_channel=256)
+            f4 = conv_bias_act(self._packs, self.flow_encoder[0], f4, "relu")
+        conv_bias_act(self._packs, self.flow_encoder[2], f4, "relu", out=hx, out_channel=256)
         with torch.autocast("cuda", enabled=False):
             glo = self.gru.global_context(net4)
         return hx, inp_pre, glo
@@ -706,7 +682,7 @@ class UpdateModule(nn.Module):
         128->128 head convolutions merged into one; same mathematics, fp16 NHWC throughout."""
         batch, num, ch, ht, wd = net.shape
         cl = torch.channels_last
-        hwc = self._hw
+        packs = self._packs
         out_dim = (batch, num, -1, ht, wd)
         n = batch * num
         net4 = net.view(n, -1, ht, wd)
@@ -726,16 +702,15 @@ class UpdateModule(nn.Module):
         if lazy is not None:        # lookup + corr_encoder[0] in one launch: the 196-channel features never reach HBM
             c4 = lazy.encoded(*self._corr_enc0_padded())
         else:
-            c4 = conv1x1_bias_act(self._head_cache, self.corr_encoder[0], c4, "relu")
-        conv_bias_act(hwc, self.corr_encoder[2], c4, "relu", out=hx, out_channel=128)
+            c4 = conv1x1_bias_act(packs, self.corr_encoder[0], c4, "relu")
+        conv_bias_act(packs, self.corr_encoder[2], c4, "relu", out=hx, out_channel=128)
         net4 = self.gru.forward_hx(net4, hx, inp_pre, glo=glo)
         net = net4.view(*out_dim)
         hw_, hb = self._head_weights()
         heads = conv_nobias(net4, hw_ if ii is not None else hw_[:256], padding=1)
-        hc = self._head_cache
         # delta[2] / weight[2] read the merged convolution's pre-activations directly (bias + ReLU on the fly)
-        delta = conv3x3_head(heads, self.delta[2], hc, "none", in_channel=0, in_bias=hb[0], in_relu=True)
-        weight = conv3x3_head(heads, self.weight[2], hc, "sigmoid", in_channel=128, in_bias=hb[1], in_relu=True)
+        delta = conv3x3_head(heads, self.delta[2], packs, "none", in_channel=0, in_bias=hb[0], in_relu=True)
+        weight = conv3x3_head(heads, self.weight[2], packs, "sigmoid", in_channel=128, in_bias=hb[1], in_relu=True)
         delta, weight = delta.view(batch, num, ht, wd, 2), weight.view(batch, num, ht, wd, 2)
         if ii is None:
             return net, delta, weight
@@ -744,25 +719,21 @@ class UpdateModule(nn.Module):
         if seg is None:
             seg = build_segments(ii.to(net.device))
         x = segment_mean_hip(heads, seg, in_channel=256, channels=128, in_bias=hb[2], in_relu=True)
-        x = conv_bias_act(hwc, agg.conv2, x, "relu")
-        eta = conv3x3_head(x, agg.eta[0], hc, "softplus", out_scale=0.01).view(batch, -1, ht, wd)
+        x = conv_bias_act(packs, agg.conv2, x, "relu")
+        eta = conv3x3_head(x, agg.eta[0], packs, "softplus", out_scale=0.01).view(batch, -1, ht, wd)
         if FUSE_UPMASK_UPSAMPLE:    # deferred: DepthVideo.upsample evaluates it fused with the convex upsampling
             upmask = LazyUpmask(self, x, (batch, -1, 8 * 8 * 9, ht, wd))
         else:
-            upmask = conv1x1_bias_act(hc, agg.upmask[0], x, "none").view(batch, -1, 8 * 8 * 9, ht, wd)
+            upmask = conv1x1_bias_act(packs, agg.upmask[0], x, "none").view(batch, -1, 8 * 8 * 9, ht, wd)
         return net, delta, weight, eta, upmask
 
     def _corr_enc0_padded(self):
         """(fp16 [128, 208] weight of corr_encoder[0] with zero-padded rows, fp32 bias) for gs_corr_lookup_enc; cached"""
-        conv = self.corr_encoder[0]
-        key = (conv.weight._version, conv.bias._version, conv.weight.device, conv.weight.data_ptr())
-        hit = self._head_cache.get("corr_enc0_pad")
-        if hit is None or hit[0] != key:
-            w = torch.zeros(128, 208, dtype=torch.float16, device=conv.weight.device)
-            w[:, :196] = conv.weight.detach().reshape(128, 196).half()
-            hit = (key, w.contiguous(), conv.bias.detach().float().contiguous())
-            self._head_cache["corr_enc0_pad"] = hit
-        return hit[1], hit[2]
+        def pad(weight):
+            w = torch.zeros(128, 208, dtype=torch.float16, device=weight.device)
+            w[:, :196] = weight.detach().reshape(128, 196).half()
+            return w
+        return conv_pack(self._packs, self.corr_encoder[0], "pad208", pad)
 
     def _fast_ok(self, net, inp, corr):
         cl = torch.channels_last

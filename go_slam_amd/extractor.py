@@ -18,6 +18,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .weight_packs import WeightPacks, conv_pack, tensors_key
+
 DIM = 32
 FAST_ENCODER = True         # module constant, not an environment switch: tests flip it to compare the two paths
 OWN_ENC_CONV = True         # gs_enc_conv for the encoder's convolutions (False: MIOpen NHWC fp16, the tests' referee)
@@ -147,6 +149,8 @@ class BasicEncoder(nn.Module):
                     nn.init.constant_(m.weight, 1)
                 if m.bias is not None:
                     nn.init.constant_(m.bias, 0)
+        self._w16 = WeightPacks()
+        self._convs = [m for m in self.modules() if isinstance(m, nn.Conv2d)]      # the hipGraph key reads them live
 
     def _conv(self, conv, x, with_bias=True, stats=None):
         """conv(x) on fp16 NHWC operands cast / packed once per weight version (what autocast computes, minus the casts).
@@ -154,21 +158,13 @@ class BasicEncoder(nn.Module):
         of conv + bias as the two fp16 tensors torch materialises).  stats=True (own kernels, InstanceNorm next): the
         convolution's epilogue also leaves the chunk moments of half(conv + bias) in this stream's norm workspace.  With `stats`
         given (True or False) a third value is returned: the `stat_chunks` to hand to _norm_act (0: none were written)."""
-        cache = self.__dict__.setdefault("_w16", {})
-        key = (conv.weight._version, conv.bias._version, conv.weight.device, conv.weight.data_ptr())
-        hit = cache.get(id(conv))
-        if hit is None or hit[0] != key:
-            hit = [key, conv.weight.detach().half().contiguous(memory_format=torch.channels_last),
-                   conv.bias.detach().half().contiguous(), None]
-            cache[id(conv)] = hit
         k, stride = conv.kernel_size[0], conv.stride[0]
         n, c, h, w = x.shape
         shape = (k, c, conv.out_channels, stride)
         if (OWN_ENC_CONV and shape in _ENC_SHAPES and x.dtype == torch.float16
                 and x.is_contiguous(memory_format=torch.channels_last) and conv.padding[0] == k // 2):
             from . import _lib
-            if hit[3] is None:
-                hit[3] = pack_enc_conv_weight(conv.weight)
+            wpack, bias = conv_pack(self._w16, conv, "enc", pack_enc_conv_weight, torch.float16)
             ho, wo = (h + 2 * (k // 2) - k) // stride + 1, (w + 2 * (k // 2) - k) // stride + 1
             y = torch.empty(n, conv.out_channels, ho, wo, dtype=torch.float16, device=x.device,
                             memory_format=torch.channels_last)
@@ -178,38 +174,27 @@ class BasicEncoder(nn.Module):
                 chunks = int(L.gs_enc_conv_stat_chunks(ho, wo, conv.out_channels))
                 ws = _stats_workspace(x.device, int(L.gs_norm_act_workspace_bytes_chunks(n, chunks, conv.out_channels)))
             with torch.cuda.device(x.device):
-                rc = L.gs_enc_conv(_lib.ptr(x), c, c, _lib.ptr(hit[3]), _lib.ptr(hit[2] if with_bias else None),
+                rc = L.gs_enc_conv(_lib.ptr(x), c, c, _lib.ptr(wpack), _lib.ptr(bias if with_bias else None),
                                    _lib.ptr(y), conv.out_channels, conv.out_channels, k, stride, n, h, w,
-                                   _lib.ptr(hit[2] if stats else None), _lib.ptr(ws), _lib.stream_ptr(x.device))
+                                   _lib.ptr(bias if stats else None), _lib.ptr(ws), _lib.stream_ptr(x.device))
             _lib.check(rc, "enc_conv")
             if stats is not None:
-                return y, hit[2], chunks
-            return y if with_bias else (y, hit[2])
+                return y, bias, chunks
+            return y if with_bias else (y, bias)
+        w16, bias = conv_pack(self._w16, conv, "nhwc", lambda t: t.detach().half().contiguous(
+            memory_format=torch.channels_last), torch.float16)
         if c == 4 and conv.in_channels == 3:            # (the stem's RGB0 input on the library path)
             x = x[:, :3].contiguous(memory_format=torch.channels_last)
         if with_bias:
-            return F.conv2d(x, hit[1], hit[2], conv.stride, conv.padding)
+            return F.conv2d(x, w16, bias, conv.stride, conv.padding)
         if stats is not None:
-            return F.conv2d(x, hit[1], None, conv.stride, conv.padding), hit[2], 0
-        return F.conv2d(x, hit[1], None, conv.stride, conv.padding), hit[2]
+            return F.conv2d(x, w16, None, conv.stride, conv.padding), bias, 0
+        return F.conv2d(x, w16, None, conv.stride, conv.padding), bias
 
     def _fast_ok(self, x):
         return (FAST_ENCODER and x.is_cuda and not torch.is_grad_enabled() and self.norm_fn in ("instance", "none")
                 and (x.dtype == torch.float16 or torch.is_autocast_enabled()) and x.shape[-1] % 8 == 0
                 and x.shape[-2] % 8 == 0)
-
-    def _packs(self, conv):
-        """(fp16 NHWC weight, fp16 bias, gs_enc_conv fragments) of a convolution, cached per weight version"""
-        cache = self.__dict__.setdefault("_w16", {})
-        key = (conv.weight._version, conv.bias._version, conv.weight.device, conv.weight.data_ptr())
-        hit = cache.get(id(conv))
-        if hit is None or hit[0] != key:
-            hit = [key, conv.weight.detach().half().contiguous(memory_format=torch.channels_last),
-                   conv.bias.detach().half().contiguous(), None]
-            cache[id(conv)] = hit
-        if hit[3] is None and OWN_ENC_CONV:
-            hit[3] = pack_enc_conv_weight(conv.weight)
-        return hit
 
     def _forward_fast(self, x):
         """The inference path.  One input frame is ~45 launches of 3-12 us each, so the HOST side decides the frame time:
@@ -248,11 +233,11 @@ class BasicEncoder(nn.Module):
             def conv(m, xin, stats):
                 k, stride, co = m.kernel_size[0], m.stride[0], m.out_channels
                 n, c, h, w = xin.shape
-                hit = self._packs(m)
+                wpack, b16 = conv_pack(self._w16, m, "enc", pack_enc_conv_weight, torch.float16)
                 ho, wo = (h + 2 * (k // 2) - k) // stride + 1, (w + 2 * (k // 2) - k) // stride + 1
                 y = torch.empty(n, co, ho, wo, dtype=torch.float16, device=dev, memory_format=cl)
-                b = hit[2].data_ptr()
-                rc = L.gs_enc_conv(xin.data_ptr(), c, c, hit[3].data_ptr(), None, y.data_ptr(), co, co, k, stride, n, h, w,
+                b = b16.data_ptr()
+                rc = L.gs_enc_conv(xin.data_ptr(), c, c, wpack.data_ptr(), None, y.data_ptr(), co, co, k, stride, n, h, w,
                                    b if stats else None, wsp if stats else None, st)
                 if rc:
                     _lib.check(rc, "enc_conv")
@@ -305,10 +290,8 @@ class BasicEncoder(nn.Module):
         return self._conv(self.conv2, y)
 
     def _weights_key(self):
-        ps = self.__dict__.get("_graph_params")
-        if ps is None:
-            ps = self.__dict__["_graph_params"] = list(self.parameters())
-        return sum(p._version for p in ps), sum(p.data_ptr() for p in ps)
+        # (each convolution's weight and bias as they are now; `m.weight` would cost nn.Module.__getattr__ 32 times a call)
+        return tensors_key([t for m in self._convs for t in m._parameters.values()])
 
     def _forward_graphed(self, x):
         """_forward_fast(x) replayed from a hipGraph: captured per (input shape, dtype, device, weight versions and

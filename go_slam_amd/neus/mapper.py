@@ -158,9 +158,7 @@ class FlatAdamW:
             torch.autograd.graph.increment_version(p)
         for mod, name in ((self.grid_module, "grid"), (self.mlp_module, "mlp")):
             a, b = self.slices[name]
-            p = mod.params
-            mod._half._val = self.P16[a:b]
-            mod._half._key = (p.data_ptr(), p._version, p.device, p.dtype)
+            mod._half.install(mod.params, self.P16[a:b])
 
     def check_bindings(self):
         """the modules' parameters must still be views of the flat buffer (a later `.half()`, `.to(device)`,
@@ -237,7 +235,7 @@ class FlatAdamW:
             return
         self._publish()
         if self._gather_wait is not None:
-            self.grid_module._half._pending = self.wait_gather
+            self.grid_module._half.set_pending(self.wait_gather)
 
     def begin_reduce_scatter(self):
         """start the reduce-scatter of the fp16 table gradient NOW (it is complete: the bin reduce has run) instead of at
@@ -250,7 +248,7 @@ class FlatAdamW:
     def wait_gather(self):
         """make the current stream wait for the deferred all-gather of the fp16 table (no-op when none is in flight)"""
         w, self._gather_wait = self._gather_wait, None
-        self.grid_module._half._pending = None
+        self.grid_module._half.set_pending(None)
         if w is not None:
             t = self._exchange_timer
             if t is not None:

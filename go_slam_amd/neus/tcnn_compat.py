@@ -26,6 +26,7 @@ import torch.nn as nn
 
 from .. import _lib
 from ..droid_backends import _workspace
+from ..weight_packs import tensors_key
 
 GS_F16, GS_F32 = 0, 1
 LOSS_SCALE = 128.0          # tcnn's default loss scale for fp16 gradients
@@ -52,11 +53,19 @@ class _HalfCache:
         if self._pending is not None:
             pend, self._pending = self._pending, None
             pend()
-        key = (p.data_ptr(), p._version, p.device, p.dtype)
+        key = tensors_key((p,))
         if self._key != key:
             self._val = p.detach().to(torch.float16).contiguous()
             self._key = key
         return self._val
+
+    def install(self, p, val):
+        """`val` is the fp16 copy of `p` as it is now (FlatAdamW's step writes it next to the master)"""
+        self._val, self._key = val, tensors_key((p,))
+
+    def set_pending(self, complete):
+        """`complete` (or None) finishes an exchange that is still writing the copy; the next get() calls it first"""
+        self._pending = complete
 
     def invalidate(self):
         self._key = None

@@ -355,8 +355,7 @@ def test_update_operator_context_term_cache_keys_and_eviction():
         calls.append(x.data_ptr())
         return x.float().sum().reshape(1)
     op.gru.inp_gates = fake_gates
-    op.gru._half_weights = lambda: None
-    op.gru._hw_key = 0
+    op.gru._weights_key = lambda: 0
     n, h, w = 3, 4, 5
     base = torch.randn(n, 128, h, w).half().contiguous(memory_format=torch.channels_last)[None]
     _, t1 = op._edge_state(base, n, h, w)
@@ -386,7 +385,7 @@ def test_update_operator_context_term_cache_keys_and_eviction():
     # debug checksum mode: a write through an alias with its own version counter (`.data`: what a raw-pointer write from a
     # HIP launch or another process looks like to torch) is served stale silently by default -- and raises in debug mode
     chk = UpdateModule()
-    chk.gru.inp_gates, chk.gru._half_weights, chk.gru._hw_key = fake_gates, (lambda: None), 0
+    chk.gru.inp_gates, chk.gru._weights_key = fake_gates, (lambda: 0)
     victim = torch.randn(n, 128, h, w).half().contiguous(memory_format=torch.channels_last)[None]
     _, v1 = chk._edge_state(victim, n, h, w)
     v = victim._version
@@ -410,7 +409,7 @@ def test_update_operator_context_term_cache_keys_and_eviction():
         op._edge_state(f, n, h, w)
     assert len(op._inp_pre_cache) == 3
     assert [k[0] for k in op._inp_pre_cache] == [f.data_ptr() for f in fresh[-3:]]
-    op.gru._hw_key = 1
+    op.gru._weights_key = lambda: 1
     op._edge_state(fresh[-1], n, h, w)
     assert len(op._inp_pre_cache) == 1
     op.drop_edge_caches()
