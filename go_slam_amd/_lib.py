@@ -141,7 +141,15 @@ SIGNATURES = {
     "gs_hull_extremes_workspace_bytes": (c_size_t, [c_int]),
     "gs_hull_extremes": (c_int, [_P, c_int, _P, _P, c_size_t, _P]),
     "gs_hull_prefilter": (c_int, [_P, c_int, _P, c_int, ctypes.c_double, _P, _P]),
-    "gs_nn_cell_keys": (c_int, [_P, c_int, _P, _P, _P, _P]),
+    "gs_mesh_visbuf_workspace_bytes": (c_size_t, []),
+    "gs_mesh_visbuf": (c_int, [_P, c_int, _P, c_int, _P, c_int] + [c_float] * 4 + [c_int, c_int, c_float, c_float, _P, _P,
+                                                                                    c_size_t, _P]),
+    "gs_line_visbuf": (c_int, [_P, c_int, ctypes.c_uint, _P, c_int] + [c_float] * 4 + [c_int, c_int, c_float, c_float, _P,
+                                                                                        _P]),
+    "gs_vertex_normals": (c_int, [_P, c_int, _P, c_int, ctypes.c_double, _P, _P, _P]),
+    "gs_visbuf_resolve": (c_int, [_P, c_int, c_int, c_int, _P, c_int, _P, c_int, _P] + [c_float] * 4
+                          + [_P, _P, c_int, _P, c_int, c_float, c_float, ctypes.c_uint, _P, _P]),
+    "gs_nn_cell_keys":(c_int, [_P, c_int, _P, _P, _P, _P]),
     "gs_nn_grid_build": (c_int, [_P, c_int, _P, _P, _P, _P, _P, _P, _P]),
     "gs_nn_query_workspace_bytes": (c_size_t, [c_int]),
     "gs_nn_query": (c_int, [_P, _P, _P, _P, c_int, _P, _P, _P, c_int, _P, ctypes.c_double, _P, _P, _P, c_size_t, _P]),

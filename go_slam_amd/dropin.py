@@ -31,9 +31,10 @@ def _torch_scatter():
     return m
 
 
-def install(droid_backends=True, tinycudann=True, lietorch=True, torch_scatter=True, datasets=False):
+def install(droid_backends=True, tinycudann=True, lietorch=True, torch_scatter=True, datasets=False, meshvideo=False):
     """datasets=True also registers go_slam_amd.datasets as `src.datasets`, so the reference's run.py resolves
-    get_dataset here (its own module imports cv2, which this stack lacks)."""
+    get_dataset here (its own module imports cv2, which this stack lacks).  meshvideo=True registers go_slam_amd.meshvideo
+    as `src.tools.meshvideo` (the reference's needs Open3D and a window)."""
     if droid_backends:
         from . import droid_backends as db
         sys.modules["droid_backends"] = db
@@ -48,3 +49,6 @@ def install(droid_backends=True, tinycudann=True, lietorch=True, torch_scatter=T
     if datasets:
         from . import datasets as ds
         sys.modules["src.datasets"] = ds
+    if meshvideo:
+        from . import meshvideo as mv
+        sys.modules["src.tools.meshvideo"] = mv

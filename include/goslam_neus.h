@@ -456,6 +456,69 @@ int gs_hull_extremes(const float* points, int n_points, int* idx, void* workspac
 int gs_hull_prefilter(const float* points, int n_points, const double* planes, int n_planes, double margin,
                       uint8_t* keep, gs_stream_t stream);
 
+/* ---- mesh video (MeshVideo, src/tools/meshvideo.py), csrc/mesh_shade.hip ----
+ * A visibility-buffer renderer: surface and line fragments compete in one uint64 buffer, a resolve pass shades what won.
+ * No float atomics and nothing that depends on arrival order: reruns are bitwise identical.  The look is this project's
+ * own contract (below), not Open3D's GL pipeline.
+ *
+ * gs_mesh_visbuf: visbuf u64 [n_poses,H,W], every word = (fp32 depth bits << 32) | face index of the nearest fragment,
+ *   all ones where there is none (the call initialises the buffer).  Arguments, coverage, near clipping, rejection rules
+ *   and the fp64 ray-plane depth are gs_mesh_depth's (same code, csrc/mesh_raster.h): the high word is gs_mesh_depth's map
+ *   bit for bit wherever that is non-zero.  One 64-bit atomicMin per fragment, so equal fp32 depths resolve to the lower
+ *   face index.  Same two launches and workspace layout as gs_mesh_depth: gs_mesh_visbuf_workspace_bytes().  H * W <= 2^24.
+ *
+ * gs_line_visbuf: world-space segments f32 [S,2,3] written into an initialised visbuf under the ids id_base + s (the host
+ *   passes id_base = n_faces; id_base + S <= 2^32 - 1).  Per (segment, pose), in fp64 with every product and sum rounded
+ *   on its own:
+ *   - both end points to camera space, P = ((M0 x + M1 y) + M2 z) + M3 per row of w2c; a segment with a non-finite
+ *     coordinate or with both z < znear draws nothing; an end point with z < znear is replaced by the crossing
+ *     A + a (B - A), a = (znear - zA) / (zB - zA), with z = znear exactly (A the end in front of the plane);
+ *   - (u, v) = (fx X / Z + cx, fy Y / Z + cy), the pixel of a point is (row floor(v), column floor(u));
+ *   - n = max(|column1 - column0|, |row1 - row0|); the n + 1 steps i = 0..n sit at t = i / n (t = 0 when n = 0) on
+ *     (u0 + t (u1 - u0), v0 + t (v1 - v0)): one pixel wide, as Open3D's LineSet; a step outside the image is skipped
+ *     (the walk only visits the steps that can be inside, so a segment that leaves the screen costs its visible part);
+ *   - the step's depth is z = 1 / (1/z0 + t (1/z1 - 1/z0)), perspective-correct along the projected line; steps with
+ *     z < znear or z > zfar are skipped; the fragment is the same atomicMin of (fp32 bits of z << 32) | id.
+ *   Lines are hidden by nearer surface and hide farther surface with no separate depth test; overlapping lines at equal
+ *   depth resolve to the lower id.  One wave per (segment, pose), lanes striding the steps.
+ *
+ * gs_vertex_normals: area-weighted vertex normals f32 [V,3] (world space), Open3D's compute_vertex_normals: the
+ *   normalised sum over a vertex' faces of (v1 - v0) x (v2 - v0).  Each face's cross product is computed in fp64 from the
+ *   fp32 vertices, each component converted to fixed point q = rint(x * scale) (int64, round to nearest even) and added to
+ *   its three vertices with integer atomics: integer addition is associative, so the sums -- sums i64 [V,3], zeroed by the
+ *   call and left for the caller to read -- and the normals are bitwise reproducible.  A second launch converts the sums
+ *   to fp64, normalises and rounds to fp32 once; a zero sum (zero-area faces only, or an unreferenced vertex) gives
+ *   (0, 0, 0).  Faces with an index outside [0, V), or whose scaled cross product is non-finite or reaches 2^62 in a
+ *   component, add nothing.  The caller chooses scale so that no sum can overflow: with extent the bounding box's
+ *   diagonal, |component| <= extent^2 per face, so scale <= 2^62 / (extent^2 * F) is safe for any valence.
+ *
+ * gs_visbuf_resolve: image u8 [n_poses,H,W,3] from a visbuf, one thread per pixel:
+ *   - an empty word (or an id that names nothing) gives `background`, packed 0xRRGGBB;
+ *   - id >= n_faces: line_colors u8 [S,3] of segment id - n_faces;
+ *   - a face: P and the canonical edge functions e0, e1, e2 of gs_mesh_depth at this pixel's ray d, recomputed in fp64;
+ *     the perspective-correct barycentric weights are (w0, w1, w2) = (e1, e2, e0) / (e0 + e1 + e2);
+ *     albedo = sum_j w_j vertex_colors[v_j] (u8 [V,3], levels 0..255), or 255 * GS_SHADE_GREY per channel when
+ *     vertex_colors is NULL; n = R sum_j w_j vertex_normals[v_j] (R = the rotation of w2c), or with flat != 0 (or
+ *     vertex_normals NULL) the face's camera-space normal s0 C0 + s1 C1 + s2 C2;
+ *     shade = ambient + diffuse * |n . d| / (|n| |d|) -- a headlight at the camera, two-sided; 0 for the cosine when
+ *     |n| = 0; channel = rint(min(max(albedo * shade, 0), 255)), rounded once (to nearest even).
+ *   The host's defaults are ambient 0.3, diffuse 0.7, a white background.                                              */
+#define GS_SHADE_GREY 0.7
+size_t gs_mesh_visbuf_workspace_bytes(void);
+int gs_mesh_visbuf(const float* vertices, int n_vertices, const int* faces, int n_faces, const float* w2c, int n_poses,
+                   float fx, float fy, float cx, float cy, int height, int width, float znear, float zfar,
+                   unsigned long long* visbuf, void* workspace, size_t workspace_bytes, gs_stream_t stream);
+int gs_line_visbuf(const float* segments, int n_segments, unsigned id_base, const float* w2c, int n_poses, float fx,
+                   float fy, float cx, float cy, int height, int width, float znear, float zfar,
+                   unsigned long long* visbuf, gs_stream_t stream);
+int gs_vertex_normals(const float* vertices, int n_vertices, const int* faces, int n_faces, double scale,
+                      long long* sums, float* normals, gs_stream_t stream);
+int gs_visbuf_resolve(const unsigned long long* visbuf, int n_poses, int height, int width, const float* vertices,
+                      int n_vertices, const int* faces, int n_faces, const float* w2c, float fx, float fy, float cx,
+                      float cy, const uint8_t* vertex_colors, const float* vertex_normals, int flat,
+                      const uint8_t* line_colors, int n_segments, float ambient, float diffuse, unsigned background,
+                      uint8_t* image, gs_stream_t stream);
+
 /* Mesh evaluation (Mesher.__call__ at the end of a run, reference src/mesher.py:309-327): exact nearest neighbours
  * between fp64 point clouds -- the two cKDTree passes of eval_mesh (src/mesher.py:390-421) and the hybrid search of the
  * Open3D point-to-point ICP behind align_mesh (src/mesher.py:339-357) -- and the moments of an ICP correspondence set.
