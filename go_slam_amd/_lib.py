@@ -88,6 +88,10 @@ SIGNATURES = {
     "gs_ba": (c_int, [_P] * 9 + [c_int] * 3 + [c_float, c_float] + [c_int] * 6 + [_P, _P, _P, _P, c_size_t, _P]),
     "gs_ba_ex": (c_int, [_P] * 9 + [c_int] * 3 + [c_float, c_float] + [c_int] * 6 + [_P, _P, _P, _P, c_size_t, c_int, _P]),
     "gs_chol_solve": (c_int, [_P, _P, c_int, c_float, c_float, c_int, _P, _P, _P]),
+    "gs_traj_eval_workspace_bytes": (c_size_t, [c_int]),
+    "gs_traj_world": (c_int, [_P, _P, c_int, _P, _P, _P]),
+    "gs_ape_moments": (c_int, [_P, _P, _P, c_int, _P, _P, c_size_t, _P]),
+    "gs_ape_stats": (c_int, [_P, _P, _P, _P, c_int, _P, _P, _P, c_size_t, _P]),
     # include/goslam_neus.h
     "gs_grid_meta_default": (c_int, [_P]),
     "gs_neus_level_major_min_points": (c_int, [c_int]),

@@ -160,6 +160,10 @@ class InstantNeuS(nn.Module):
     def update_bound(self, bound):
         self.realtime_bound[:] = bound.float().to(self.realtime_bound.device)
         self._host_bounds = None
+        # re-read the host copy now, not at the next forward: that forward may be the one MapTrainer captures into a graph
+        # (its eager warm-ups can lie before this call, as when the mapper runs once per keyframe), and a capture cannot
+        # copy to the host
+        self._bounds_host()
 
     @staticmethod
     def in_bound(pts, bound):

@@ -171,3 +171,48 @@ def plane_disps(poses, intr, ht, wd):
         z = (c - t[..., axis]) / ray[..., axis]
         best = torch.minimum(best, torch.where(z > 0.1, z, torch.full_like(z, float("inf"))))
     return torch.where(torch.isfinite(best), 1.0 / best, torch.zeros_like(best)).float()
+
+
+def arc_poses(n, step_m=0.03, step_deg=0.5):
+    """World-to-camera poses [n, 7] of a camera that drifts forward and sideways on an arc with a slow yaw about y,
+    looking at plane_disps' wall and floor."""
+    from .lietorch_shim import SE3
+    k = torch.arange(n, dtype=torch.float64)
+    yaw = math.radians(step_deg) * k
+    pos = torch.stack([step_m * k + 0.05 * torch.sin(0.2 * k), 0.02 * torch.sin(0.13 * k), 0.5 * step_m * k], 1)
+    q = torch.stack([torch.zeros(n, dtype=torch.float64), torch.sin(yaw / 2), torch.zeros(n, dtype=torch.float64),
+                     torch.cos(yaw / 2)], 1)
+    return SE3(torch.cat([pos, q], 1)).inv().data.float()
+
+
+class PlaneSequence:
+    """An in-memory RGB-D sequence with the dataset interface (`__len__`, iteration, `poses`, `input_folder`,
+    `image_timestamps`): plane_disps' wall and floor seen from arc_poses, coloured by a smooth function of the world
+    point, so colour, depth and poses agree.  Items are (index, image [1,3,H,W] in [0,1], depth [H,W] in m,
+    intrinsic [4], camera-to-world [4,4]) on the host, as the dataset readers yield them."""
+
+    def __init__(self, n, H, W, fx, fy, cx, cy, poses=True, timestamps=False):
+        from .lietorch_shim import SE3
+        self.n, self.input_folder = n, "synthetic plane sequence"
+        self.intrinsic = torch.tensor([fx, fy, cx, cy], dtype=torch.float32)
+        w2c = arc_poses(n)
+        c2w = SE3(w2c.double()).inv()
+        disp = plane_disps(w2c, self.intrinsic, H, W).double()
+        self.depths = torch.where(disp > 0, 1.0 / disp.clamp(min=1e-6), torch.zeros_like(disp)).float()
+        v, u = torch.meshgrid(torch.arange(H, dtype=torch.float64), torch.arange(W, dtype=torch.float64), indexing="ij")
+        cam = torch.stack([(u - cx) / fx, (v - cy) / fy, torch.ones_like(u)], -1)[None] * self.depths.double()[..., None]
+        world = c2w[:, None, None] * cam
+        freq = torch.tensor([[2.1, 3.3, 1.7], [4.3, 1.9, 2.9], [1.3, 5.1, 3.7]], dtype=torch.float64)
+        self.images = (0.5 + 0.5 * torch.sin(world @ freq.T)).permute(0, 3, 1, 2).float().contiguous()
+        self.c2w = c2w.matrix().float()
+        self.poses = [m.numpy().copy() for m in self.c2w] if poses else None
+        self.image_timestamps = [0.1 * i for i in range(n)] if timestamps else None
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, i):
+        return i, self.images[i][None].clone(), self.depths[i].clone(), self.intrinsic.clone(), self.c2w[i].clone()
+
+    def __iter__(self):
+        return (self[i] for i in range(self.n))

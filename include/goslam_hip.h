@@ -494,6 +494,34 @@ int gs_edge_prep(const float* raw, float* d_work, const long long* ex_i, const l
 int gs_edge_greedy(const float* raw, const float* sorted_vals, const long long* order, long long* es, int* count,
                    int cap, int i0, int j0, int t, int nms, float thresh, int max_factors, int loop, gs_stream_t stream);
 
+/* End-of-run trajectory evaluation on the device, fp64 (src/slam.py:313-365).  Every reduction below has one fixed
+ * order -- frame 256 b + t belongs to thread t of block b, an LDS tree (stride 128 .. 1) inside the block, then one
+ * block that adds the block results b = t, t + 256, ... in ascending order and runs the same tree -- and uses no
+ * float atomics: two runs give identical bits.  workspace: gs_traj_eval_workspace_bytes(n) for both reductions.
+ *
+ * gs_traj_world (replaces src/slam.py:315-318, `SE3(pose_compensate) * traj.inv()`, `.data` and `.matrix()`):
+ *   w2c f32 [n,7] world-to-camera (t, q), compensate f32 [7]; tq f64 [n,7] = compensate * inv(w2c) as (t, q) and
+ *   mat f64 [n,4,4] the same pose as a camera-to-world matrix (rotation = the quaternion's action on the basis, not
+ *   normalised, as lietorch's matrix()).  fp32 inputs are widened first; one thread per frame.
+ *
+ * gs_ape_moments (replaces the sums inside evo's umeyama_alignment, reached from src/slam.py:359-360):
+ *   est, ref f64 [n,3]; mask u8 [n] (NULL = every frame), a frame with mask 0 is never read.  moments f64 [17]:
+ *   [0] valid count, [1..3] mean of est, [4..6] mean of ref, [7..15] the 3x3 cross-covariance
+ *   sum (ref - mean_ref)(est - mean_est)^T / count row-major with ref along the rows, [16] the variance of est
+ *   sum |est - mean_est|^2 / count.  Two passes: the means, then the centred sums.  count == 0 gives zeros.
+ *
+ * gs_ape_stats (replaces evo's APE translation part and its statistics, src/slam.py:359-364):
+ *   sim f64 [12] on the device: c R row-major [9] then t [3].  err f64 [n]: |ref - (cR est + t)| per frame, -1 for a
+ *   frame outside the mask.  stats f64 [7] = rmse, mean, median, min, max, sse, std (population) over the valid
+ *   frames.  The median is taken by rank counting (rank = #{j: e_j < e_i or e_j == e_i and j < i}): the frames of
+ *   rank (count - 1) / 2 and count / 2 are averaged.  count == 0 gives NaN statistics (sse 0).                 */
+size_t gs_traj_eval_workspace_bytes(int n);
+int gs_traj_world(const float* w2c, const float* compensate, int n, double* tq, double* mat, gs_stream_t stream);
+int gs_ape_moments(const double* est, const double* ref, const unsigned char* mask, int n, double* moments,
+                   void* workspace, size_t workspace_bytes, gs_stream_t stream);
+int gs_ape_stats(const double* est, const double* ref, const unsigned char* mask, const double* sim, int n,
+                 double* err, double* stats, void* workspace, size_t workspace_bytes, gs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
