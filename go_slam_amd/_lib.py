@@ -54,6 +54,9 @@ SIGNATURES = {
     "gs_pointcloud_mask": (c_int, [_P, _P] + [c_int] * 4 + [_P, c_size_t, _P]),
     "gs_pointcloud_scan": (c_int, [c_int] * 3 + [_P, c_size_t, _P, _P]),
     "gs_pointcloud_emit": (c_int, [_P] * 5 + [c_int] * 4 + [_P, c_size_t, ctypes.c_longlong, _P, _P, _P]),
+    "gs_tsdf_batch": (c_int, []),
+    "gs_tsdf_integrate": (c_int, [_P] * 3 + [c_int] * 3 + [_P] * 4 + [c_int] * 3 + [c_float] * 10 + [_P]),
+    "gs_tsdf_vertex_attr": (c_int, [_P, c_int, _P, _P, c_int, c_int, c_int, c_float, _P, _P, _P]),
     "gs_frame_prep_color": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P]),
     "gs_frame_prep_depth": (c_int, [_P, c_int, c_float, c_int, c_int, c_int, c_int, _P]),
     "gs_cvx_upsample":(c_int, [_P] * 4 + [c_int] * 4 + [_P]),

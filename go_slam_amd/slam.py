@@ -191,7 +191,9 @@ class SLAM:
     def terminate(self, rank=-1, stream=None):
         """Fill in the poses of the non-keyframes, evaluate the trajectory and write the run's files (slam.py:289-370):
         checkpoints/go.ckpt, checkpoints/est_poses.npy, then submission.txt without ground truth or metrics_traj.txt with
-        it, and the final mesh.  Returns the statistics (an empty dict without ground truth)."""
+        it, and the final mesh.  With cfg["tsdf"]["enable"] also mesh/tsdf_mesh.ply, the keyframe depth fused into a TSDF
+        (tsdf.fuse_from_config; this one also under only_tracking).  Returns the statistics (an empty dict without ground
+        truth)."""
         os.makedirs(f"{self.output}/checkpoints/", exist_ok=True)
         torch.save({"mapping_net": self.mapping_net.state_dict(), "tracking_net": self.net.state_dict(),
                     "keyframe_timestamps": self.video.timestamp}, f"{self.output}/checkpoints/go.ckpt")
@@ -230,5 +232,8 @@ class SLAM:
         if self.meshing_finished > 0 and not self.only_tracking:
             self.mesher(the_end=True, estimate_c2w_list=estimate_c2w_list, gt_c2w_list=gt_c2w_list,
                         trans_init=trans_init)
+        if (self.cfg.get("tsdf") or {}).get("enable", False):     # mesh/tsdf_mesh.ply, also under only_tracking
+            from .tsdf import fuse_from_config
+            fuse_from_config(self, trans_init=trans_init)
         print("Terminate: Done!")
         return stats

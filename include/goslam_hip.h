@@ -202,6 +202,45 @@ int gs_pointcloud_emit(const float* poses_inv, const float* disps, const float* 
                        const int64_t* index, int k, int num, int h, int w, const void* workspace,
                        size_t workspace_bytes, long long n_points, float* points, float* colors, gs_stream_t stream);
 
+/* ---- TSDF fusion of keyframe depth (no counterpart in the reference), csrc/tsdf.hip ----
+ *
+ * State on a dense lattice of nx x ny x nz points, z contiguous, each size in [2, 1024] (gs_mcubes_*'s limit; anything
+ * else returns GS_ERR_INVALID_ARG and launches nothing): tsdf f32 [nx,ny,nz] initialised to +1 by the caller, weight
+ * f32 [nx,ny,nz] initialised to 0, colors f32 [3,nx,ny,nz] (planar RGB) initialised to 0.  Offsets are 64-bit.
+ *
+ * gs_tsdf_integrate: k frames, in the given order, GS_TSDF_BATCH per launch.  depth f32 [k,h,w] in metres along the
+ *   optical axis (<= 0: invalid), mask f32 [k,h,w] or NULL (0 drops the pixel), images f32 [k,3,h,w] or NULL (the
+ *   colour lattice is then neither read nor written and may be NULL), w2c f32 [k,3,4] world-to-camera matrices, rows
+ *   (r0 r1 r2 t).  fx, fy > 0.  Per lattice point (i,j,k) and frame, in fp32, one rounding per operation, no fma:
+ *
+ *     p   = lo + float(idx) * voxel                       (per axis)
+ *     pc  = R p + t   as ((r0*px + r1*py) + r2*pz) + t    (per row)
+ *     skip if !(pc.z > 1e-3)
+ *     u = fx * (pc.x / pc.z) + cx ; v = fy * (pc.y / pc.z) + cy
+ *     fu = floorf(u + 0.5f) ; fv likewise ; skip unless 0 <= fu < w and 0 <= fv < h ; iu = (int)fu ; iv = (int)fv
+ *     d = depth[iv,iu] ; skip if !(d > 0) or mask[iv,iu] == 0
+ *     sdf = d - pc.z ; skip if sdf < -trunc
+ *     s = fminf(1.0f, sdf / trunc)
+ *     w1 = w0 + 1.0f
+ *     tsdf = (tsdf * w0 + s) / w1
+ *     if sdf <= trunc: colour = (colour * w0 + images[:,iv,iu]) / w1   (per channel)
+ *     w = fminf(w1, max_weight)
+ *
+ *   One lane owns a point: no atomics, results independent of the launch geometry and of how k is cut into calls.
+ * gs_tsdf_vertex_attr: vertices f32 [n_vertices,3] of gs_mcubes_emit over that lattice (index space; at most one
+ *   coordinate c of a vertex is fractional).  a = floor of every coordinate; b = a, plus one along the first axis with
+ *   t = c - floorf(c) > 0 (t = 0 and b = a when there is none); both clamped into the lattice.
+ *   keep u8 [n_vertices] = weight[a] >= min_weight && weight[b] >= min_weight;
+ *   rgb f32 [n_vertices,3] = colors[a] + t * (colors[b] - colors[a]) per channel.                                   */
+#define GS_TSDF_BATCH 16
+int gs_tsdf_batch(void);
+int gs_tsdf_integrate(float* tsdf, float* weight, float* colors, int nx, int ny, int nz, const float* depth,
+                      const float* mask, const float* images, const float* w2c, int k, int h, int w, float fx, float fy,
+                      float cx, float cy, float lo_x, float lo_y, float lo_z, float voxel, float trunc,
+                      float max_weight, gs_stream_t stream);
+int gs_tsdf_vertex_attr(const float* vertices, int n_vertices, const float* weight, const float* colors, int nx, int ny,
+                        int nz, float min_weight, unsigned char* keep, float* rgb, gs_stream_t stream);
+
 /* ---- frame preprocessing of the dataset readers (src/datasets.py:96-143, 565-605), csrc/frame_prep.hip ----
  *
  * Semantics: tests/frame_prep_restatement.py, bit for bit (cv2.remap / cv2.resize INTER_LINEAR on 8-bit data,
