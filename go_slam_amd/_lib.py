@@ -76,6 +76,8 @@ SIGNATURES = {
     "gs_conv3x3_gru_zr2": (c_int, [_P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "gs_conv3x3_gru_q": (c_int, [_P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "gs_conv3x3_head": (c_int, [_P, c_int, _P, c_int, _P, _P, c_int, c_int, c_float, _P, c_int, c_int, c_int, _P]),
+    "gs_conv3x3_heads": (c_int, [_P, c_int, c_int, _P, c_int, _P, _P, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "gs_conv3x3_heads_finish": (c_int, [_P, _P, _P, c_int, c_int, c_float, c_float, _P, _P, c_int, c_int, c_int, _P]),
     "gs_segment_mean": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, c_int, c_int, c_int, _P]),
     "gs_norm_act_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "gs_norm_act": (c_int, [_P, _P, _P, _P] + [c_int] * 6 + [c_float, _P, c_size_t, c_int, _P]),

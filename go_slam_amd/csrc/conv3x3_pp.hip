@@ -80,6 +80,13 @@ __device__ __forceinline__ void pp_glds16(const void* src, void* lds_wave_base) 
 //                                     z = aux0, net = aux1; the convolution's input is [x (first `split` channels,
 //                                     stride xs) | xb (stride xsb)], i.e. [r * net | corr, flow features] without a cat.
 //   EPI 3 (any width):                y = relu(pre + b); y / ys may address a channel slice of a wider tensor.
+//   EPI 4 (merged head convolution):   the first n_tap channel blocks (delta[0], weight[0]) have NO fp16 output: their
+//                                     128 channels are reduced, per pixel, to the 18 tap products of the 3x3 head that
+//                                     reads them (delta[2] / weight[2]) -- relu(pre + b) in fp16 times the head's packed
+//                                     tap weights on MFMA, conv3x3_head_kernel's operand arithmetic and accumulation order,
+//                                     so the products are its LDS tile's values bit for bit -- and written as fp32
+//                                     tap_out[block][pixel][18]; gs_conv3x3_heads_finish gathers the 9 taps.  Later blocks
+//                                     (agg.conv1) are stored as EPI 0 does, y / ys addressing channel block n_tap onwards.
 struct PpEpi {
   const float* bias;           // [256] (EPI 1) / [128] (EPI 2) / [n_out] (EPI 3)
   const float* glo;            // [n, 256] / [n, 128] global-context terms
@@ -90,6 +97,9 @@ struct PpEpi {
   _Float16* out1;              // EPI 1: r * net             [n*h*w, 128]
   const _Float16* xb;          // EPI 2: second input source (channels >= split)
   int xsb, split;
+  const half8* tapw;           // EPI 4: [n_tap][8][64] A fragments of the 128 -> 2 heads (gs_conv3x3_head's wpack)
+  float* tap_out;              // EPI 4: [n_tap][n*h*w][18] tap products
+  int n_tap;                   // EPI 4: channel blocks that end as tap products
   // Read by the PROBE instantiation only (built with -DGS_BUILD_PROBES for tools/conv3x3_pp_probe.py; the production
   // instantiations contain no trace of them): per-workgroup s_memtime stamps, and A/B bits -- 1 = no s_setprio around
   // the MFMAs, 2 = read phase without masks, 4 = no LDS-DMA in the main loop (stale operands), 8 = no fragment reads in
@@ -320,7 +330,93 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(const _Float16* __re
 
   // ---- epilogue: [32 pixels][64 channels] at a time through a wave-private LDS tile (aliases patch buffer 0)
   _Float16* tile = reinterpret_cast<_Float16*>(smem) + wv * 32 * PP_TS;
-  _Float16* yb = y + nb * PP_BN + wn * (PP_BN / 2);
+  _Float16* yb = y + (EPI == 4 ? nb - ep.n_tap : nb) * PP_BN + wn * (PP_BN / 2);
+  if constexpr (EPI == 4) {
+    if (nb < ep.n_tap) {                                  // the same for every wave of the workgroup
+      // Waves wn = 0 / 1 of a pixel quarter hold channels 0-63 / 64-127 of the same pixels: k-steps 0-3 / 4-7 of the
+      // head's product.  wn = 0 starts from zero and hands its 16 accumulator registers over through LDS; wn = 1 goes
+      // on from them -- one accumulation chain in conv3x3_head_kernel's order.  The hand-over slots (4 KB per pair,
+      // two per pair: wn = 0 fills fragment i + 1's while wn = 1 drains fragment i's) lie behind the eight tiles.
+      typedef float float4v __attribute__((ext_vector_type(4)));
+      typedef float float2v __attribute__((ext_vector_type(2)));
+      float4v* const hand = reinterpret_cast<float4v*>(reinterpret_cast<_Float16*>(smem) + 8 * 32 * PP_TS);
+      static_assert((8 * 32 * PP_TS * 2) % 16 == 0 && 8 * 32 * PP_TS * 2 + 2 * 4 * 4096 <= 2 * PSLOTS * 16, "hand-over");
+      half8 ta[4];
+      float tb[4][8];
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        ta[ks] = ep.tapw[((size_t)nb * 8 + wn * 4 + ks) * 64 + lane];
+        const float* bb = ep.bias + nb * 128 + wn * 64 + 16 * ks + 8 * kgl;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) tb[ks][e] = bb[e];
+      }
+      float* const tp = ep.tap_out + (size_t)nb * ((size_t)rows * W) * 18;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            half4 o;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = (_Float16)acc[j][i][4 * g + e];
+            *reinterpret_cast<half4*>(tile + r * PP_TS + j * 32 + 8 * g + 4 * kgl) = o;
+          }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        half8 t[4];                                       // B operand: pixel r, channels 16 ks + 8 kgl ... + 8
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+          t[ks] = *reinterpret_cast<const half8*>(tile + r * PP_TS + 16 * ks + 8 * kgl);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            float f = (float)t[ks][e] + tb[ks][e];
+            f = fmaxf(f, 0.0f);
+            t[ks][e] = (_Float16)f;
+          }
+        }
+        float4v* const hp = hand + (((i & 1) * 4 + wm) * 4) * 64 + lane;
+        float16v c;
+        if (wn == 0) {
+#pragma unroll
+          for (int e = 0; e < 16; ++e) c[e] = 0.0f;
+#pragma unroll
+          for (int ks = 0; ks < 4; ++ks) c = __builtin_amdgcn_mfma_f32_32x32x16_f16(ta[ks], t[ks], c, 0, 0, 0);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const float4v v = {c[4 * q], c[4 * q + 1], c[4 * q + 2], c[4 * q + 3]};
+            hp[q * 64] = v;
+          }
+        }
+        __syncthreads();
+        if (wn == 1) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const float4v v = hp[q * 64];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) c[4 * q + e] = v[e];
+          }
+#pragma unroll
+          for (int ks = 0; ks < 4; ++ks) c = __builtin_amdgcn_mfma_f32_32x32x16_f16(ta[ks], t[ks], c, 0, 0, 0);
+          int ty, tx;
+          tile_pixel<TW, true>(wm, i, r, ty, tx);
+          const int gv = g0 + ty, gx = tx0 + tx;
+          if (gv < rows && gx < W) {                      // C layout: row = (reg & 3) + 8 (reg >> 2) + 4 kgl < 18, col = pixel
+            float* o = tp + ((size_t)gv * W + gx) * 18 + 4 * kgl;
+            *reinterpret_cast<float2v*>(o) = float2v{c[0], c[1]};
+            *reinterpret_cast<float2v*>(o + 2) = float2v{c[2], c[3]};
+            *reinterpret_cast<float2v*>(o + 8) = float2v{c[4], c[5]};
+            *reinterpret_cast<float2v*>(o + 10) = float2v{c[6], c[7]};
+            if (kgl == 0) *reinterpret_cast<float2v*>(o + 16) = float2v{c[8], c[9]};
+          }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+      }
+      return;
+    }
+  }
   constexpr int PIECES = NJ * 4;                          // 16-byte pieces per pixel row of this wave's channels (8 / 4)
   constexpr int PXIT = 64 / PIECES;                       // pixels covered per store round (8 / 16)
   constexpr int NIT = 32 / PXIT;                          // store rounds per 32-pixel fragment (4 / 2)
@@ -376,7 +472,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(const _Float16* __re
       if (ok4[it]) {
         const half8 v = *reinterpret_cast<const half8*>(tile + pxr * PP_TS + piece * 8);
         const size_t pix = pix4[it];
-        if constexpr (EPI == 0) {
+        if constexpr (EPI == 0 || EPI == 4) {
           *reinterpret_cast<half8*>(yb + pix * ys + piece * 8) = v;
         } else if constexpr (EPI == 3) {
           const float* bb = ep.bias + nb * PP_BN + c8;
@@ -561,6 +657,30 @@ extern "C" int gs_conv3x3_bias_relu(const void* x, int x_stride, int c_in, const
                               (hipStream_t)stream, ep);
   return dispatch_pp<3>(x, x_stride, c_in, wpack, pp_tile_width(w), y, y_stride, n_out, n, h, w, 1, (hipStream_t)stream,
                         ep);
+}
+
+// The merged head convolution (delta[0] | weight[0] | agg.conv1, EPI 4): the first n_tap_blocks 128-channel blocks leave as
+// tap products for gs_conv3x3_heads_finish, the others as fp16 rows of y (channel block n_tap_blocks = y's channel 0).
+extern "C" int gs_conv3x3_heads(const void* x, int x_stride, int c_in, const void* wpack, int tw, const void* tap_wpack,
+                                const float* in_bias, int n_tap_blocks, float* tap_out, void* y, int y_stride, int n_out,
+                                int n, int h, int w, gs_stream_t stream) {
+  GS_REQUIRE(x && wpack && tap_wpack && in_bias && tap_out, "conv3x3_heads: null pointer");
+  GS_REQUIRE(tw == 8 || tw == 16, "conv3x3_heads: tile width must be 8 or 16");
+  GS_REQUIRE(c_in > 0 && c_in % 32 == 0, "conv3x3_heads: c_in must be a multiple of 32");
+  GS_REQUIRE(n_out > 0 && n_out % 128 == 0, "conv3x3_heads: n_out must be a multiple of 128");
+  GS_REQUIRE(n_tap_blocks >= 1 && n_tap_blocks <= n_out / 128, "conv3x3_heads: n_tap_blocks must be in [1, n_out / 128]");
+  GS_REQUIRE(x_stride >= c_in && x_stride % 8 == 0, "conv3x3_heads: x_stride must be >= c_in and a multiple of 8");
+  const int rest = n_out - 128 * n_tap_blocks;
+  GS_REQUIRE(rest == 0 || (y && y_stride >= rest && y_stride % 8 == 0),
+             "conv3x3_heads: y / y_stride must hold the %d channels behind the tap blocks", rest);
+  GS_REQUIRE(n >= 0 && h > 0 && w > 0, "conv3x3_heads: bad shape");
+  if (n == 0) return GS_OK;
+  PpEpi ep = PpEpi();
+  ep.bias = in_bias;
+  ep.tapw = (const half8*)tap_wpack;
+  ep.tap_out = tap_out;
+  ep.n_tap = n_tap_blocks;
+  return dispatch_pp<4>(x, x_stride, c_in, wpack, tw, y, y_stride, n_out, n, h, w, 1, (hipStream_t)stream, ep);
 }
 
 extern "C" size_t gs_conv3x3_wpack_elems(int c_in, int n_out) { return (size_t)9 * c_in * n_out; }

@@ -130,6 +130,72 @@ __global__ __launch_bounds__(256) void conv3x3_head_kernel(
   }
 }
 
+// Second half of the two 128 -> 2 heads when the merged head convolution has already reduced every pixel to its 18 tap
+// products (gs_conv3x3_heads): a workgroup copies the products of its HEAD_ROWS + 2 image rows -- contiguous in T, so the
+// reads are whole cache lines; gathering the 9 taps straight from global memory at a 72-byte pixel stride took 35 us at
+// 75 x 60 x 80 -- into conv3x3_head_kernel's LDS tile and runs its gather and epilogue, same order, same expressions, for
+// both heads (blockIdx.z) in one launch.  T: [2][n*h*w][18] fp32.
+struct HeadsFinish {
+  const float* bias[2];
+  float* out[2];
+  int epilogue[2];
+  float scale[2];
+};
+
+__global__ __launch_bounds__(256) void conv3x3_heads_finish_kernel(const float* __restrict__ T, HeadsFinish p, int h, int w) {
+  constexpr int O = 2, NT = 9 * O, S = NT | 1;            // the LDS tile of conv3x3_head_kernel, filled from T
+  typedef float float2v __attribute__((ext_vector_type(2)));
+  extern __shared__ float cs[];                           // [(HEAD_ROWS + 2) * w][S]
+  const int n = blockIdx.y, hd = blockIdx.z;
+  const int r0 = blockIdx.x * HEAD_ROWS;
+  const int in_lo = max(r0 - 1, 0), in_hi = min(r0 + HEAD_ROWS, h - 1);
+  const int npx = (in_hi - in_lo + 1) * w;
+  const int tid = threadIdx.x;
+  const size_t npix = (size_t)gridDim.y * h * w;
+  // the rows of a workgroup are contiguous in T: 72 B per pixel, read as consecutive 8-byte pieces
+  const float2v* src = reinterpret_cast<const float2v*>(T + ((size_t)hd * npix + (size_t)(n * h + in_lo) * w) * NT);
+  for (int i = tid; i < npx * (NT / 2); i += 256) {
+    const float2v v = src[i];
+    const int px = i / (NT / 2), c = 2 * (i - (NT / 2) * px);
+    cs[px * S + c] = v[0];
+    cs[px * S + c + 1] = v[1];
+  }
+  __syncthreads();
+
+  const float* bias = p.bias[hd];
+  const int epilogue = p.epilogue[hd];
+  const float out_scale = p.scale[hd];
+  float* out = p.out[hd];
+  const int nrow = min(HEAD_ROWS, h - r0);
+  for (int idx = tid; idx < nrow * w; idx += 256) {
+    const int r = r0 + idx / w, cc = idx % w;
+    float acc[O];
+#pragma unroll
+    for (int o = 0; o < O; ++o) acc[o] = 0.0f;
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky) {
+      const int rr = r + ky - 1;
+      if (rr < 0 || rr >= h) continue;
+#pragma unroll
+      for (int kx = 0; kx < 3; ++kx) {
+        const int c2 = cc + kx - 1;
+        if (c2 < 0 || c2 >= w) continue;
+        const float* q = cs + ((rr - in_lo) * w + c2) * S + (ky * 3 + kx) * O;
+#pragma unroll
+        for (int o = 0; o < O; ++o) acc[o] += q[o];
+      }
+    }
+    float* op = out + ((size_t)(n * h + r) * w + cc) * O;
+#pragma unroll
+    for (int o = 0; o < O; ++o) {
+      float v = (float)(_Float16)(acc[o] + bias[o]);                 // the convolution's fp16 output
+      if (epilogue == 1) v = (float)(_Float16)gs_sigmoid(v);                          // sigmoid (fp16 op)
+      else if (epilogue == 2) v = (v > 20.0f) ? v : log1pf(__expf(v));                // softplus (fp32 op)
+      op[o] = v * out_scale;
+    }
+  }
+}
+
 template <int O>
 int launch_head(const void* x, int ldx, const float* in_bias, int in_relu, const void* wpack, const float* bias,
                 int epilogue, float out_scale, float* out, int n, int h, int w, hipStream_t st) {
@@ -158,4 +224,29 @@ extern "C" int gs_conv3x3_head(const void* x, int x_stride, const float* in_bias
   hipStream_t st = (hipStream_t)stream;
   return n_out == 1 ? launch_head<1>(x, x_stride, in_bias, in_relu, wpack, bias, epilogue, out_scale, out, n, h, w, st)
                     : launch_head<2>(x, x_stride, in_bias, in_relu, wpack, bias, epilogue, out_scale, out, n, h, w, st);
+}
+
+extern "C" int gs_conv3x3_heads_finish(const float* tap, const float* bias0, const float* bias1, int epilogue0,
+                                       int epilogue1, float out_scale0, float out_scale1, float* out0, float* out1, int n,
+                                       int h, int w, gs_stream_t stream) {
+  GS_REQUIRE(tap && bias0 && bias1 && out0 && out1, "conv3x3_heads_finish: null pointer");
+  GS_REQUIRE(epilogue0 >= 0 && epilogue0 <= 2 && epilogue1 >= 0 && epilogue1 <= 2,
+             "conv3x3_heads_finish: epilogue in {0 none, 1 sigmoid, 2 softplus}");
+  GS_REQUIRE(n >= 0 && h > 0 && w > 0, "conv3x3_heads_finish: bad shape");
+  if (n == 0) return GS_OK;
+  const long long npix = (long long)n * h * w;
+  GS_REQUIRE(npix < (1ll << 29), "conv3x3_heads_finish: too many pixels");
+  HeadsFinish p;
+  p.bias[0] = bias0; p.bias[1] = bias1;
+  p.out[0] = out0; p.out[1] = out1;
+  p.epilogue[0] = epilogue0; p.epilogue[1] = epilogue1;
+  p.scale[0] = out_scale0; p.scale[1] = out_scale1;
+  GS_REQUIRE(n <= 65535, "conv3x3_heads_finish: at most 65535 images");
+  const size_t lds = (size_t)(HEAD_ROWS + 2) * w * 19 * sizeof(float);
+  GS_REQUIRE(lds <= 160 * 1024, "conv3x3_heads_finish: image width %d needs %zu bytes of LDS", w, lds);
+  static GsLdsLimit limit;
+  if (int rc = limit.raise((const void*)conv3x3_heads_finish_kernel, lds, "conv3x3_heads_finish")) return rc;
+  conv3x3_heads_finish_kernel<<<dim3(gs_cdiv(h, HEAD_ROWS), n, 2), 256, lds, (hipStream_t)stream>>>(tap, p, h, w);
+  GS_CHECK_LAUNCH("conv3x3_heads_finish");
+  return GS_OK;
 }

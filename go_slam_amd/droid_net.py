@@ -152,6 +152,45 @@ def conv3x3_head(x, conv, cache, epilogue="none", out_scale=1.0, in_channel=0, i
     return out
 
 
+def pack_heads_tap_weights(weights):
+    """gs_conv3x3_heads' tap_wpack for the 128 -> 2 heads that read channel blocks 0, 1, ... of the merged head
+    convolution: their gs_conv3x3_head images stacked, fp16 [len(weights), 8, 64, 8]."""
+    assert all(tuple(w.shape) == (2, 128, 3, 3) for w in weights)
+    return torch.stack([pack_head_weight(w) for w in weights]).contiguous()
+
+
+def heads_workspace_shapes(n, h, w, n_out, n_tap):
+    """(tap products fp32 [n_tap, n*h*w, 18], compact NHWC rows [n, h, w, n_out - 128 n_tap] or None) of
+    gs_conv3x3_heads for a merged convolution of n_out channels whose first n_tap 128-channel blocks end as tap products;
+    column (3 ky + kx) * 2 + o of a pixel's 18 is its contribution to output o of the pixel at (-(ky - 1), -(kx - 1))."""
+    assert n_out % 128 == 0 and 1 <= n_tap <= n_out // 128
+    rest = n_out - 128 * n_tap
+    return (n_tap, n * h * w, 18), ((n, h, w, rest) if rest else None)
+
+
+def conv3x3_heads_fused(x, w, tap_wpack, in_bias, taps, rest, bias0, bias1, epilogues=("none", "sigmoid"), tw=None):
+    """The merged head convolution `w` [128 k, C, 3, 3] over NHWC fp16 x with the two 128 -> 2 heads finished from its
+    epilogue (gs_conv3x3_heads + gs_conv3x3_heads_finish): returns the heads' fp32 [n,h,w,2] outputs; `taps` / `rest` are
+    the caller's workspaces (heads_workspace_shapes; `rest` receives the channel blocks behind the first two)."""
+    from . import _lib
+    image = conv3x3_weight_image(w, 32)
+    n, c, h, wd = x.shape
+    O = w.shape[0]
+    epi = {"none": 0, "sigmoid": 1, "softplus": 2}
+    out0 = torch.empty(n, h, wd, 2, dtype=torch.float32, device=x.device)
+    out1 = torch.empty(n, h, wd, 2, dtype=torch.float32, device=x.device)
+    L = _lib.lib()
+    with torch.cuda.device(x.device):
+        st = _lib.stream_ptr(x.device)
+        rc = L.gs_conv3x3_heads(_lib.ptr(x), c, c, _lib.ptr(image), tw or conv3x3_pp_tile_width(wd), _lib.ptr(tap_wpack),
+                                _lib.ptr(in_bias), 2, _lib.ptr(taps), _lib.ptr(rest), O - 256, O, n, h, wd, st)
+        _lib.check(rc, "conv3x3_heads")
+        rc = L.gs_conv3x3_heads_finish(_lib.ptr(taps), _lib.ptr(bias0), _lib.ptr(bias1), epi[epilogues[0]],
+                                       epi[epilogues[1]], 1.0, 1.0, _lib.ptr(out0), _lib.ptr(out1), n, h, wd, st)
+        _lib.check(rc, "conv3x3_heads_finish")
+    return out0, out1
+
+
 def cvx_upsample(data, mask):
     """Convex 8x upsampling (src/droid_net.py:9-23): data [b,h,w,d], mask [b,576,h,w]."""
     b, h, w, d = data.shape
@@ -195,6 +234,10 @@ GRU_GLO_FUSED = True
 # GraphAgg's upmask convolution (128 -> 576) fused with DepthVideo.upsample's convex upsampling (gs_upmask_upsample): the
 # update operator returns a LazyUpmask; False: gs_conv1x1 writes the mask, gs_cvx_upsample reads it (the tests' referee)
 FUSE_UPMASK_UPSAMPLE = True
+# delta[2] / weight[2] finished from the merged head convolution's epilogue (gs_conv3x3_heads + gs_conv3x3_heads_finish: the
+# 256 channels of delta[0] | weight[0] never reach HBM); False: gs_conv3x3_pp writes all 384 channels and gs_conv3x3_head
+# reads them back twice (the tests' referee for the fusion, bit-identical)
+FUSE_HEAD_TAPS = True
 # correlation lookup fused with corr_encoder[0] (gs_corr_lookup_enc) when the caller hands a corr.LazyLookup; False:
 # gs_corr_lookup_pyramid + gs_conv1x1 (the tests' referee for the fusion)
 FUSE_LOOKUP_ENCODER = True
@@ -662,6 +705,35 @@ class UpdateModule(nn.Module):
             return w, [m.bias.detach().float().contiguous() for m in mods]
         return self._packs.get("heads", [m.weight for m in mods] + [m.bias for m in mods], build)
 
+    def _head_taps(self):
+        """(tap_wpack of delta[2] | weight[2], their producers' biases as one fp32 [256], bias of delta[2], of weight[2])"""
+        mods = (self.delta[0], self.weight[0], self.delta[2], self.weight[2])
+
+        def build():
+            return (pack_heads_tap_weights([self.delta[2].weight, self.weight[2].weight]),
+                    torch.cat([self.delta[0].bias, self.weight[0].bias]).detach().float().contiguous(),
+                    self.delta[2].bias.detach().float().contiguous(), self.weight[2].bias.detach().float().contiguous())
+        return self._packs.get("head_taps", [m.weight for m in mods] + [m.bias for m in mods], build)
+
+    HEADS_WS_ENTRIES = 4            # shapes whose workspaces are kept (frontend window, motion filter, backend chunks)
+
+    def _heads_workspace(self, n, ht, wd, n_out, device):
+        """(tap products, compact agg.conv1 pre-activations or None) of the fused head path, kept per shape like `_hx`:
+        both are consumed inside the update that fills them."""
+        ws = self.__dict__.setdefault("_heads_ws", {})
+        key = (n, ht, wd, n_out, device)
+        hit = ws.pop(key, None)
+        if hit is None:
+            ts, rs = heads_workspace_shapes(n, ht, wd, n_out, 2)
+            taps = torch.empty(ts, dtype=torch.float32, device=device)
+            rest = None if rs is None else torch.empty((n, rs[3], ht, wd), dtype=torch.float16, device=device,
+                                                       memory_format=torch.channels_last)
+            hit = (taps, rest)
+            while len(ws) >= self.HEADS_WS_ENTRIES:
+                ws.pop(next(iter(ws)))
+        ws[key] = hit
+        return hit
+
     def _corr_independent_part(self, net4, inp, f4, n, ht, wd):
         """everything of the fast path that does not need the correlation features: the GRU input buffer with net and the
         flow-encoder features in place, the hoisted context term, the GRU's global-context terms"""
@@ -707,10 +779,19 @@ class UpdateModule(nn.Module):
         net4 = self.gru.forward_hx(net4, hx, inp_pre, glo=glo)
         net = net4.view(*out_dim)
         hw_, hb = self._head_weights()
-        heads = conv_nobias(net4, hw_ if ii is not None else hw_[:256], padding=1)
-        # delta[2] / weight[2] read the merged convolution's pre-activations directly (bias + ReLU on the fly)
-        delta = conv3x3_head(heads, self.delta[2], packs, "none", in_channel=0, in_bias=hb[0], in_relu=True)
-        weight = conv3x3_head(heads, self.weight[2], packs, "sigmoid", in_channel=128, in_bias=hb[1], in_relu=True)
+        hw_ = hw_ if ii is not None else hw_[:256]
+        fused = FUSE_HEAD_TAPS and _use_own_conv3x3(net4, hw_, 1, 1)
+        if fused:       # the heads' tap products leave the convolution's epilogue; agg.conv1's block lands compact
+            tapw, tapb, b_delta, b_weight = self._head_taps()
+            taps, heads = self._heads_workspace(n, ht, wd, hw_.shape[0], net4.device)
+            delta, weight = conv3x3_heads_fused(net4, hw_, tapw, tapb, taps, heads, b_delta, b_weight)
+            agg_channel = 0
+        else:
+            heads = conv_nobias(net4, hw_, padding=1)
+            # delta[2] / weight[2] read the merged convolution's pre-activations directly (bias + ReLU on the fly)
+            delta = conv3x3_head(heads, self.delta[2], packs, "none", in_channel=0, in_bias=hb[0], in_relu=True)
+            weight = conv3x3_head(heads, self.weight[2], packs, "sigmoid", in_channel=128, in_bias=hb[1], in_relu=True)
+            agg_channel = 256
         delta, weight = delta.view(batch, num, ht, wd, 2), weight.view(batch, num, ht, wd, 2)
         if ii is None:
             return net, delta, weight
@@ -718,7 +799,7 @@ class UpdateModule(nn.Module):
         agg = self.agg
         if seg is None:
             seg = build_segments(ii.to(net.device))
-        x = segment_mean_hip(heads, seg, in_channel=256, channels=128, in_bias=hb[2], in_relu=True)
+        x = segment_mean_hip(heads, seg, in_channel=agg_channel, channels=128, in_bias=hb[2], in_relu=True)
         x = conv_bias_act(packs, agg.conv2, x, "relu")
         eta = conv3x3_head(x, agg.eta[0], packs, "softplus", out_scale=0.01).view(batch, -1, ht, wd)
         if FUSE_UPMASK_UPSAMPLE:    # deferred: DepthVideo.upsample evaluates it fused with the convex upsampling

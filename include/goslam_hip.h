@@ -386,6 +386,22 @@ int gs_conv3x3_gru_q(const void* rnet, const void* x_rest, int x_rest_stride, in
 int gs_conv3x3_head(const void* x, int x_stride, const float* in_bias, int in_relu, const void* wpack,
                     const float* bias, int n_out, int epilogue, float out_scale, float* out, int n, int h, int w,
                     gs_stream_t stream);
+/* The merged head convolution delta[0] | weight[0] | agg.conv1 (src/droid_net.py:83,88,40) with the 128 -> 2 heads that
+ * read its first blocks finished in its epilogue: gs_conv3x3_pp's kernel, arguments and weight image; the first
+ * n_tap_blocks 128-channel blocks are never written as fp16 -- each pixel's relu(pre + in_bias) (fp16) is multiplied with
+ * that block's head weights (tap_wpack: [n_tap_blocks] gs_conv3x3_head images, fp16 [8][64][8] each; in_bias f32
+ * [128 n_tap_blocks]) in gs_conv3x3_head's operand arithmetic and accumulation order, and the 18 products go to
+ * tap_out f32 [n_tap_blocks][n*h*w][18], column (3 ky + kx) 2 + o.  The remaining n_out / 128 - n_tap_blocks blocks are
+ * stored without bias as gs_conv3x3_pp does, into y [n*h*w, y_stride] from channel 0 (y may be NULL when there are none).
+ * gs_conv3x3_heads_finish: out_k[n,h,w,2] = out_scale_k * epi_k(half(sum over the 9 in-image taps of
+ * tap[k][neighbour][tap column] + bias_k)) for the two heads k = 0, 1 -- gs_conv3x3_head's gather and epilogue, so the
+ * pair equals gs_conv3x3_pp + 2 x gs_conv3x3_head(in_bias, in_relu = 1) bit for bit.                              */
+int gs_conv3x3_heads(const void* x, int x_stride, int c_in, const void* wpack, int tw, const void* tap_wpack,
+                     const float* in_bias, int n_tap_blocks, float* tap_out, void* y, int y_stride, int n_out, int n,
+                     int h, int w, gs_stream_t stream);
+int gs_conv3x3_heads_finish(const float* tap, const float* bias0, const float* bias1, int epilogue0, int epilogue1,
+                            float out_scale0, float out_scale1, float* out0, float* out1, int n, int h, int w,
+                            gs_stream_t stream);
 /* GraphAgg's scatter_mean over source keyframes (src/droid_net.py:57-60, torch_scatter):
  * out[s, p, :] = mean over k in [seg_offsets[s], seg_offsets[s+1]) of act(x[seg_edges[k], p, :]), NHWC
  * fp16 [*, hw, channels] (channels % 8 == 0, x rows x_stride elements apart), fp32 accumulation.
