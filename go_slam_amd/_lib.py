@@ -114,6 +114,9 @@ SIGNATURES = {
                              + [c_int, c_int, _P]),
     "gs_render_img_metrics_workspace_bytes": (c_size_t, []),
     "gs_render_img_metrics": (c_int, [_P] * 7 + [c_int, c_int] + [_P] * 5 + [c_size_t, _P]),
+    "gs_image_quality_tile": (c_int, [ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "gs_image_quality_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "gs_image_quality": (c_int, [_P] * 4 + [c_int, c_int, _P, _P, c_size_t, _P]),
     "gs_neus_backward_rays": (c_int, [_P] * 13 + [c_int, c_int, _P]),
     "gs_mapping_loss": (c_int, [_P] * 8 + [c_float] * 4 + [c_int] + [_P] * 4 + [c_int, c_int, _P]),
     "gs_map_grad_sqnorm": (c_int, [_P, c_size_t, c_float, _P, c_size_t, _P, _P]),

@@ -192,8 +192,10 @@ class SLAM:
         """Fill in the poses of the non-keyframes, evaluate the trajectory and write the run's files (slam.py:289-370):
         checkpoints/go.ckpt, checkpoints/est_poses.npy, then submission.txt without ground truth or metrics_traj.txt with
         it, and the final mesh.  With cfg["tsdf"]["enable"] also mesh/tsdf_mesh.ply, the keyframe depth fused into a TSDF
-        (tsdf.fuse_from_config; this one also under only_tracking).  Returns the statistics (an empty dict without ground
-        truth)."""
+        (tsdf.fuse_from_config; this one also under only_tracking).  With cfg["render_eval"]["enable"] (keys enable, every,
+        save_images) and a map, also metrics_render.txt: PSNR, SSIM and depth L1 of the map's renderings against the input
+        frames (neus/render_eval.py), their means under `render_*` keys of the returned statistics.  Returns the
+        statistics (an empty dict without ground truth and without that step)."""
         os.makedirs(f"{self.output}/checkpoints/", exist_ok=True)
         torch.save({"mapping_net": self.mapping_net.state_dict(), "tracking_net": self.net.state_dict(),
                     "keyframe_timestamps": self.video.timestamp}, f"{self.output}/checkpoints/go.ckpt")
@@ -232,6 +234,14 @@ class SLAM:
         if self.meshing_finished > 0 and not self.only_tracking:
             self.mesher(the_end=True, estimate_c2w_list=estimate_c2w_list, gt_c2w_list=gt_c2w_list,
                         trans_init=trans_init)
+        render_cfg = self.cfg.get("render_eval") or {}
+        if render_cfg.get("enable", False) and not self.only_tracking:     # metrics_render.txt
+            from .neus.render_eval import REPORT_ORDER, eval_rendering
+            res = eval_rendering(self, stream, estimate_c2w_list, every=render_cfg.get("every", 5),
+                                 out_path=f"{self.output}/metrics_render.txt",
+                                 save_images=render_cfg.get("save_images", False))
+            stats.update({f"render_{k}": res[k] for k in REPORT_ORDER})
+            print("Rendering: " + ", ".join(f"{k} {res[k]!r}" for k in REPORT_ORDER))
         if (self.cfg.get("tsdf") or {}).get("enable", False):     # mesh/tsdf_mesh.ply, also under only_tracking
             from .tsdf import fuse_from_config
             fuse_from_config(self, trans_init=trans_init)

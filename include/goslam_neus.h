@@ -164,6 +164,30 @@ int gs_render_img_metrics(const float* color, const float* depth, const float* n
                           float* normal_cam, float* depth_res, float* color_res, double* metrics,
                           void* workspace, size_t workspace_bytes, gs_stream_t stream);
 
+/* ---- rendering evaluation (neus/render_eval.py), csrc/image_quality.hip ----
+ * Quality of a rendered frame against the input frame, over the WHOLE image (gs_render_img_metrics above is the
+ * visualiser's: pixels with depth only).  pred_rgb, gt_rgb f32 [H,W,3] interleaved, not clipped; pred_depth, gt_depth
+ * f32 [H,W], both NULL or neither.
+ *   -> out DEVICE f64 [8] = { mse, psnr, ssim, depth_l1, n_depth, n_windows, 0, 0 }:
+ *   mse      mean of (pred - gt)^2 over the 3 H W values; psnr = -10 log10(mse) (data range 1; +inf at mse == 0);
+ *   depth_l1 mean of |pred_depth - gt_depth| over the n_depth pixels with gt_depth > 0 (NaN and 0 without such a pixel
+ *            or without the depth pair);
+ *   ssim     Wang et al. 2004 per channel: 11 x 11 Gaussian window, sigma 1.5, weights the outer product of the
+ *            normalised g_k = exp(-(k-5)^2 / 4.5) / sum; valid windows only, no padding: (H-10) x (W-10) positions per
+ *            channel, n_windows = 3 (H-10)(W-10).  Per window mu_x, mu_y, E[x^2], E[y^2], E[xy]; var = E[x^2] - mu_x^2,
+ *            cov = E[xy] - mu_x mu_y; s = (2 mu_x mu_y + C1)(2 cov + C2) / ((mu_x^2 + mu_y^2 + C1)(var_x + var_y + C2))
+ *            with C1 = 0.01^2, C2 = 0.03^2; ssim = the mean of s.
+ * Inputs are fp32, every moment and sum is fp64; fixed-order reductions (no atomics): the same bits on every run.  NaN
+ * inputs give NaN outputs.  H < 11 or W < 11: GS_ERR_INVALID_ARG before any launch.  The kernel works on tiles of
+ * GS_IQ_TILE_H x GS_IQ_TILE_W window positions (gs_image_quality_tile reads them back from the library); workspace:
+ * gs_image_quality_workspace_bytes(H, W), one fp64 partial per sum and tile (0 for a refused size).                */
+#define GS_IQ_TILE_H 16
+#define GS_IQ_TILE_W 32
+int gs_image_quality_tile(int* tile_h, int* tile_w);
+size_t gs_image_quality_workspace_bytes(int H, int W);
+int gs_image_quality(const float* pred_rgb, const float* gt_rgb, const float* pred_depth, const float* gt_depth,
+                     int H, int W, double* out, void* workspace, size_t workspace_bytes, gs_stream_t stream);
+
 /* Backward of InstantNeuS.forward, stage 1 (per ray): from the upstream gradients of the ray
  * outputs -- d_color [n,3], d_depth [n], d_depth_var [n], d_normal [n,3], d_weight_sum [n] --
  * and the saved per-point alpha / rgb / z_mid / grad / mask, produce d_alpha f32 [n,s] (w.r.t. the
