@@ -361,7 +361,9 @@ class InstantNeuS(nn.Module):
         bnd = gt - z
         sm = (bnd.abs() <= self.sdf_truncation) & vm
         nvs = front.sum(1) + sm.sum(1) + 1e-8
-        nvr = vm.sum()
+        # with no valid ray both numerators are exact zeros: dividing them by 1 instead of 0 keeps the values' 0 and makes
+        # the backward 0 instead of 0 / 0 (a NaN that the gradient all-reduce would hand to every rank); nvr >= 1 is untouched
+        nvr = vm.sum().clamp(min=1)
         fl = torch.max(torch.exp((-self.sdf_sparse_factor * pred).clamp(max=10.0)) - torch.ones_like(pred),
                        pred - bnd).clamp(min=0.0) * front
         return ((torch.abs(pred - bnd) * sm).sum(1) / nvs).sum() / nvr, (fl.sum(1) / nvs).sum() / nvr
