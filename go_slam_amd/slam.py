@@ -192,7 +192,9 @@ class SLAM:
         """Fill in the poses of the non-keyframes, evaluate the trajectory and write the run's files (slam.py:289-370):
         checkpoints/go.ckpt, checkpoints/est_poses.npy, then submission.txt without ground truth or metrics_traj.txt with
         it, and the final mesh.  With cfg["tsdf"]["enable"] also mesh/tsdf_mesh.ply, the keyframe depth fused into a TSDF
-        (tsdf.fuse_from_config; this one also under only_tracking).  With cfg["render_eval"]["enable"] (keys enable, every,
+        (tsdf.fuse_from_config; this one also under only_tracking), and with cfg["tsdf"]["eval_depth"]["enable"] (keys
+        enable, every, save_images) metrics_tsdf_depth.txt: that volume raycast at the estimated poses against the sensor
+        depth, the means under `tsdf_*` keys of the returned statistics.  With cfg["render_eval"]["enable"] (keys enable, every,
         save_images) and a map, also metrics_render.txt: PSNR, SSIM and depth L1 of the map's renderings against the input
         frames (neus/render_eval.py), their means under `render_*` keys of the returned statistics.  Returns the
         statistics (an empty dict without ground truth and without that step)."""
@@ -244,6 +246,6 @@ class SLAM:
             print("Rendering: " + ", ".join(f"{k} {res[k]!r}" for k in REPORT_ORDER))
         if (self.cfg.get("tsdf") or {}).get("enable", False):     # mesh/tsdf_mesh.ply, also under only_tracking
             from .tsdf import fuse_from_config
-            fuse_from_config(self, trans_init=trans_init)
+            fuse_from_config(self, stream=stream, trans_init=trans_init, c2w_list=estimate_c2w_list, stats=stats)
         print("Terminate: Done!")
         return stats

@@ -5,6 +5,11 @@ csrc/tsdf.hip integrates depth maps at given world-to-camera poses into a dense 
 batch of frames per launch, no atomics), `neus.mesh.marching_cubes` meshes it, and a second kernel drops the vertices
 next to never-observed points and colours the rest.  Arithmetic contract: include/goslam_hip.h (gs_tsdf_*);
 tests/tsdf_restatement.py restates it serially.
+
+csrc/tsdf_raycast.hip looks at the volume from a camera: `TSDFVolume.raycast` marches every pixel's ray to the first
+zero crossing and returns depth, normal and colour images, and `eval_tsdf_depth` compares those depth images with the
+sensor's at the end of a run (metrics_tsdf_depth.txt).  tests/tsdf_raycast_restatement.py restates the march (DESIGN.md
+section 22).
 """
 import math
 import os
@@ -32,6 +37,28 @@ def w2c_matrices(w2c):
     else:
         raise ValueError(f"w2c must be [K,7], [K,4,4] or [K,3,4] (got {tuple(w2c.shape)})")
     return m.to(torch.float32).contiguous()
+
+
+def c2w_matrices(w2c):
+    """float32 [K,3,4] camera-to-world matrices from world-to-camera poses in the forms `w2c_matrices` accepts ([K,7],
+    [K,4,4], [K,3,4]; rigid).  The inverse (R^T, -R^T t) is formed in float64 on the tensor's device and rounded once."""
+    w2c = torch.as_tensor(w2c)
+    if w2c.dim() == 2 and w2c.shape[1] == 7:
+        m = SE3(w2c.double()).inv().matrix()[:, :3, :]
+    elif w2c.dim() == 3 and tuple(w2c.shape[1:]) in ((4, 4), (3, 4)):
+        rt = w2c[:, :3, :3].double().transpose(1, 2)
+        m = torch.cat([rt, -(rt @ w2c[:, :3, 3:].double())], dim=2)
+    else:
+        raise ValueError(f"w2c must be [K,7], [K,4,4] or [K,3,4] (got {tuple(w2c.shape)})")
+    return m.to(torch.float32).contiguous()
+
+
+def _intrinsics4(intrinsics, what):
+    intr = list(intrinsics) if isinstance(intrinsics, (tuple, list)) else \
+        torch.as_tensor(intrinsics).detach().cpu().reshape(-1).tolist()
+    if len(intr) != 4:
+        raise ValueError(f"{what}: intrinsics must be (fx, fy, cx, cy)")
+    return [float(v) for v in intr]
 
 
 class TSDFVolume:
@@ -65,9 +92,11 @@ class TSDFVolume:
         self.tsdf = torch.empty(self.dims, dtype=torch.float32, device=self.device)
         self.weight = torch.empty(self.dims, dtype=torch.float32, device=self.device)
         self.colors = torch.empty((3,) + self.dims, dtype=torch.float32, device=self.device)
+        self._flags = None         # raycast's brick flags, dropped by whatever changes tsdf (reset, integrate)
         self.reset()
 
     def reset(self):
+        self._flags = None
         self.tsdf.fill_(1.0)
         self.weight.zero_()
         self.colors.zero_()
@@ -95,21 +124,81 @@ class TSDFVolume:
             raise ValueError(f"TSDFVolume.integrate: {mats.shape[0]} poses for {K} depth maps")
         images = None if images is None else f32(images, "images", (K, 3, H, W))
         mask = None if mask is None else f32(mask, "mask", (K, H, W))
-        intr = torch.as_tensor(intrinsics).detach().cpu().reshape(-1).tolist() if not isinstance(intrinsics, (tuple, list)) \
-            else list(intrinsics)
-        if len(intr) != 4:
-            raise ValueError("TSDFVolume.integrate: intrinsics must be (fx, fy, cx, cy)")
+        intr = _intrinsics4(intrinsics, "TSDFVolume.integrate")
         if K == 0:
             return self
         nx, ny, nz = self.dims
+        self._flags = None
         with torch.cuda.device(dev):
             rc = _lib.lib().gs_tsdf_integrate(
                 _lib.ptr(self.tsdf), _lib.ptr(self.weight), _lib.ptr(self.colors), nx, ny, nz, _lib.ptr(depth),
-                _lib.ptr(mask), _lib.ptr(images), _lib.ptr(mats), K, H, W, *[float(v) for v in intr],
+                _lib.ptr(mask), _lib.ptr(images), _lib.ptr(mats), K, H, W, *intr,
                 float(self.lo[0]), float(self.lo[1]), float(self.lo[2]), self.voxel, self.trunc, self.max_weight,
                 _lib.stream_ptr(dev))
         _lib.check(rc, "TSDFVolume.integrate")
         return self
+
+    @torch.no_grad()
+    def brick_flags(self):
+        """uint8 [bx,by,bz], b = ceil((n - 1) / 8): 1 where a brick of 8 x 8 x 8 cells has a corner with tsdf < 0
+        (gs_tsdf_brick_flags).  Kept until `integrate` or `reset` changes the volume; code that writes `.tsdf` itself
+        sets `_flags = None` afterwards."""
+        if self._flags is None:
+            nx, ny, nz = self.dims
+            flags = torch.empty(tuple((n - 1 + 7) // 8 for n in self.dims), dtype=torch.uint8, device=self.device)
+            assert flags.numel() == _lib.lib().gs_tsdf_brick_flags_bytes(nx, ny, nz)
+            with torch.cuda.device(self.device):
+                rc = _lib.lib().gs_tsdf_brick_flags(_lib.ptr(self.tsdf), nx, ny, nz, _lib.ptr(flags),
+                                                    _lib.stream_ptr(self.device))
+            _lib.check(rc, "TSDFVolume.brick_flags")
+            self._flags = flags
+        return self._flags
+
+    @torch.no_grad()
+    def raycast(self, w2c, intrinsics, size, near=0.0, far=math.inf, step=0.5, min_weight=1.0, color=True, skip=True):
+        """The first zero crossing of the volume along every pixel's ray (gs_tsdf_raycast): {"depth": [K,H,W] in metres
+        along the optical axis, 0 without a hit, "normal": [K,H,W,3] unit, world frame, toward free space, "color":
+        [K,H,W,3] or None}, float32 on the volume's device.  w2c as `integrate` takes it (one pose list serves both);
+        intrinsics (fx, fy, cx, cy) of the size = (H, W) images; `step` is the march's step in voxels, in (0, 1]; a cell
+        counts only where all eight corners were seen `min_weight` times.  skip=False marches without the brick flags:
+        same bits, slower.  Enqueues on the current stream; nothing is read back.  ValueError for bad shapes or ranges."""
+        return self._raycast(c2w_matrices(w2c), intrinsics, size, near, far, step, min_weight, color, skip)
+
+    def _raycast(self, c2w, intrinsics, size, near=0.0, far=math.inf, step=0.5, min_weight=1.0, color=True, skip=True):
+        """`raycast` from float32 [K,3,4] camera-to-world matrices."""
+        what = "TSDFVolume.raycast"
+        intr = _intrinsics4(intrinsics, what)
+        if len(tuple(size)) != 2 or int(size[0]) < 1 or int(size[1]) < 1:
+            raise ValueError(f"{what}: size must be (H, W) with H, W >= 1 (got {size})")
+        H, W = int(size[0]), int(size[1])
+        near, far, step, min_weight = float(near), float(far), float(step), float(min_weight)
+        if not (intr[0] != 0 and intr[1] != 0):
+            raise ValueError(f"{what}: fx and fy must not be zero")
+        if not (near >= 0 and far > near):
+            raise ValueError(f"{what}: need 0 <= near < far (got near {near}, far {far})")
+        if not (0 < step <= 1):
+            raise ValueError(f"{what}: step must lie in (0, 1] voxels (got {step})")
+        if math.ceil(sum(self.dims) / step) + 2 > 2 ** 24:
+            raise ValueError(f"{what}: step {step} needs more than 2^24 steps across this lattice")
+        if c2w.dim() != 3 or tuple(c2w.shape[1:]) != (3, 4):
+            raise ValueError(f"{what}: camera-to-world matrices must be [K,3,4] (got {list(c2w.shape)})")
+        dev = self.device
+        c2w = c2w.to(device=dev, dtype=torch.float32).contiguous()
+        K = int(c2w.shape[0])
+        depth = torch.empty(K, H, W, dtype=torch.float32, device=dev)
+        normal = torch.empty(K, H, W, 3, dtype=torch.float32, device=dev)
+        rgb = torch.empty(K, H, W, 3, dtype=torch.float32, device=dev) if color else None
+        if K > 0:
+            flags = self.brick_flags() if skip else None
+            nx, ny, nz = self.dims
+            with torch.cuda.device(dev):
+                rc = _lib.lib().gs_tsdf_raycast(
+                    _lib.ptr(self.tsdf), _lib.ptr(self.weight), _lib.ptr(self.colors) if color else None, nx, ny, nz,
+                    _lib.ptr(flags), _lib.ptr(c2w), K, H, W, *intr, float(self.lo[0]), float(self.lo[1]),
+                    float(self.lo[2]), self.voxel, near, far, step, min_weight, _lib.ptr(depth), _lib.ptr(normal),
+                    _lib.ptr(rgb), _lib.stream_ptr(dev))
+            _lib.check(rc, what)
+        return {"depth": depth, "normal": normal, "color": rgb}
 
     @torch.no_grad()
     def vertex_attr(self, verts, min_weight=1.0):
@@ -200,18 +289,135 @@ def fuse_keyframes(video, bound, voxel_size, source="tracked", index=None, trunc
     return vol, vol.extract_mesh(min_weight)
 
 
-def fuse_from_config(slam, stream=None, trans_init=None):
+DEPTH_REPORT_ORDER = ("depth_l1_cm", "coverage", "n_frames")     # order of the lines of metrics_tsdf_depth.txt
+EVAL_CHUNK = 16                                                  # frames per raycast in eval_tsdf_depth
+
+
+def depth_metrics_text(result, frames, per_frame, metric_depth=True):
+    """The text of metrics_tsdf_depth.txt: two header lines, `name<TAB>value` per reported value, then one line per
+    evaluated frame, `index depth_l1 coverage n_depth` (depth_l1 in m).  Values are written with repr(): reading the file
+    gives back the fp64 numbers bit for bit."""
+    why = "depth L1 over the pixels with a hit and sensor depth > 0" if metric_depth else \
+        "nan and no frames: without sensor depth (mode is not rgbd) there is nothing metric to compare with"
+    lines = ["Raycast of the TSDF volume against the sensor depth: depth L1 (first zero crossing along each pixel's ray, "
+             "depth along the optical axis), coverage (share of the pixels with sensor depth that have a hit)",
+             f"(means over the evaluated frames; {why}; then per frame: index depth_l1[m] coverage n_depth)"]
+    lines += [f"{k}\t{result[k]!r}" for k in DEPTH_REPORT_ORDER]
+    rows = np.asarray(per_frame, dtype=np.float64).reshape(len(frames), 4)
+    lines += [f"{int(i)} {float(r[0])!r} {float(r[1])!r} {int(r[2])}" for i, r in zip(frames, rows)]
+    return "\n".join(lines) + "\n"
+
+
+def parse_depth_metrics(text):
+    """depth_metrics_text's inverse: (reported dict, [(index, depth_l1, coverage, n_depth), ...])."""
+    lines = text.splitlines()
+    if len(lines) < 2 + len(DEPTH_REPORT_ORDER) or not lines[0].startswith("Raycast of the TSDF volume"):
+        raise ValueError("not a metrics_tsdf_depth.txt")
+    result = {}
+    for key, line in zip(DEPTH_REPORT_ORDER, lines[2:]):
+        name, value = line.split("\t")
+        if name != key:
+            raise ValueError(f"metrics_tsdf_depth.txt: expected {key}, found {name}")
+        result[key] = int(value) if key == "n_frames" else float(value)
+    frames = []
+    for line in lines[2 + len(DEPTH_REPORT_ORDER):]:
+        i, d, c, n = line.split(" ")
+        frames.append((int(i), float(d), float(c), int(n)))
+    return result, frames
+
+
+def summarize_depth(frames, per_frame):
+    """frames: the evaluated indices; per_frame: host fp64 [F,4] (depth_l1 in m, coverage, n_depth, n_valid).  -> the
+    reported dict: the mean depth_l1 in cm over the frames with a compared pixel, the mean coverage over the frames with
+    sensor depth, and n_frames."""
+    from .neus.render_eval import frame_mean
+    rows = np.asarray(per_frame, dtype=np.float64).reshape(len(frames), 4)
+    return {"depth_l1_cm": 100.0 * frame_mean([r[0] for r in rows if r[2] > 0]),
+            "coverage": frame_mean([r[1] for r in rows if r[3] > 0]), "n_frames": len(frames)}
+
+
+@torch.no_grad()
+def eval_tsdf_depth(vol, stream, c2w_list, intrinsics, every=5, out_path=None, save_images=False, step=0.5,
+                    min_weight=1.0, metric_depth=True, return_images=False):
+    """Raycast `vol` at every `every`-th frame of `stream` from its camera-to-world pose c2w_list[i] ([4,4] or [3,4], the
+    volume's frame: what terminate holds as estimate_c2w_list) and compare the depth image with the frame's sensor
+    depth.  Per frame: depth_l1 [m] over the pixels with both a hit and sensor depth > 0, n_depth their number, coverage
+    = n_depth / the number of pixels with sensor depth.  The sums are fp64 on the device, kept in one [F,4] tensor and
+    read once.  Returns summarize_depth()'s dict plus `frames` and `per_frame` (host fp64 [F,4]: depth_l1, coverage,
+    n_depth, n_valid), with `return_images` also `depth` and `hit` ([F,H,W], on the device); with `out_path` writes that
+    file, with `save_images` also tsdf_eval/{i:05d}.jpg beside it: the normal map as (n + 1) / 2 | the input frame.
+    metric_depth=False (the run had no sensor depth): nothing is raycast, the file says why and holds nan."""
+    every = int(every)
+    if every < 1:
+        raise ValueError("eval_tsdf_depth: every must be at least 1")
+    if save_images and out_path is None:
+        raise ValueError("eval_tsdf_depth: save_images needs out_path (the images go beside it)")
+    dev = vol.device
+    img_dir = None
+    if save_images and metric_depth:
+        img_dir = os.path.join(os.path.dirname(os.path.abspath(out_path)), "tsdf_eval")
+        os.makedirs(img_dir, exist_ok=True)
+    frames = list(range(0, len(stream), every)) if metric_depth else []
+    rows, depths = [], []
+    for a in range(0, len(frames), EVAL_CHUNK):
+        ids = frames[a:a + EVAL_CHUNK]
+        items = [stream[i] for i in ids]
+        gt = torch.stack([it[2].to(dev, torch.float32) for it in items])
+        c2w = torch.stack([torch.as_tensor(c2w_list[i])[:3, :] for i in ids]).to(torch.float32)
+        out = vol._raycast(c2w, intrinsics, tuple(gt.shape[1:]), step=step, min_weight=min_weight,
+                           color=False)
+        pred = out["depth"]
+        valid = gt > 0
+        both = valid & (pred > 0)
+        n_valid, n_depth = valid.sum(dim=(1, 2)).double(), both.sum(dim=(1, 2)).double()
+        l1 = ((pred.double() - gt.double()).abs() * both).sum(dim=(1, 2)) / n_depth
+        rows.append(torch.stack([l1, n_depth / n_valid, n_depth, n_valid], dim=1))
+        if return_images:
+            depths.append(pred)
+        if img_dir is not None:
+            from .neus.render_eval import _interleaved, _save_side_by_side
+            for j, i in enumerate(ids):
+                colour = _interleaved(items[j][1], "the stream's colour").to(dev, torch.float32)
+                _save_side_by_side(os.path.join(img_dir, f"{i:05d}.jpg"), (out["normal"][j] + 1.0) * 0.5, colour)
+    per_frame = (torch.cat(rows) if rows else torch.zeros(0, 4, dtype=torch.float64)).cpu().numpy()      # the one read
+    result = summarize_depth(frames, per_frame)
+    if out_path is not None:
+        with open(out_path, "w") as fh:
+            fh.write(depth_metrics_text(result, frames, per_frame, metric_depth=metric_depth))
+    result.update(frames=frames, per_frame=per_frame)
+    if return_images:
+        result["depth"] = torch.cat(depths) if depths else torch.zeros(0, 0, 0, device=dev)
+        result["hit"] = result["depth"] > 0
+    return result
+
+
+def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=None):
     """`SLAM.terminate`'s TSDF step: with cfg["tsdf"]["enable"], fuse the run's keyframes, write
     {output}/mesh/tsdf_mesh.ply and, with a readable meshing.gt_mesh_path and meshing.eval_rec, align and evaluate it
-    into {output}/metrics_tsdf_mesh.txt.  Returns the Mesh, or None when the key is absent or disabled."""
+    into {output}/metrics_tsdf_mesh.txt.  With cfg["tsdf"]["eval_depth"]["enable"] (keys enable, every, save_images;
+    absent by default) also raycast the fused volume at the poses `c2w_list` of the frames of `stream` and compare with
+    their sensor depth (eval_tsdf_depth) into {output}/metrics_tsdf_depth.txt, the means under `tsdf_*` keys of the dict
+    `stats`.  Returns the Mesh, or None when the key is absent or disabled."""
     opt = slam.cfg.get("tsdf") or {}
     if not opt.get("enable", False):
         return None
     bound = opt.get("bound") or slam.cfg["mapping"]["bound"]
-    _, mesh = fuse_keyframes(slam.video, bound, float(opt.get("voxel_size", 0.05)), source=opt.get("source", "tracked"),
-                             trunc=opt.get("truncation"), min_weight=float(opt.get("min_weight", 1.0)))
+    min_weight = float(opt.get("min_weight", 1.0))
+    vol, mesh = fuse_keyframes(slam.video, bound, float(opt.get("voxel_size", 0.05)), source=opt.get("source", "tracked"),
+                               trunc=opt.get("truncation"), min_weight=min_weight)
     os.makedirs(f"{slam.output}/mesh", exist_ok=True)
     mesh.export(f"{slam.output}/mesh/tsdf_mesh.ply")
+    ev = opt.get("eval_depth") or {}
+    if ev.get("enable", False):
+        if stream is None or c2w_list is None:
+            raise ValueError("fuse_from_config: tsdf.eval_depth needs the stream and its camera-to-world poses")
+        res = eval_tsdf_depth(vol, stream, c2w_list, (slam.video.intrinsics[0] * 8).cpu().tolist(),
+                              every=ev.get("every", 5), out_path=f"{slam.output}/metrics_tsdf_depth.txt",
+                              save_images=ev.get("save_images", False), min_weight=min_weight,
+                              metric_depth=slam.mode == "rgbd")
+        if stats is not None:
+            stats.update({f"tsdf_{k}": res[k] for k in DEPTH_REPORT_ORDER})
+        print("TSDF depth: " + ", ".join(f"{k} {res[k]!r}" for k in DEPTH_REPORT_ORDER))
     meshing = slam.cfg.get("meshing") or {}
     gt_path = meshing.get("gt_mesh_path") or ""
     if meshing.get("eval_rec") and gt_path.find(".ply") > -1 and os.path.exists(gt_path) and len(mesh.faces) > 0:

@@ -241,6 +241,62 @@ int gs_tsdf_integrate(float* tsdf, float* weight, float* colors, int nx, int ny,
 int gs_tsdf_vertex_attr(const float* vertices, int n_vertices, const float* weight, const float* colors, int nx, int ny,
                         int nz, float min_weight, unsigned char* keep, float* rgb, gs_stream_t stream);
 
+/* ---- raycast of that TSDF lattice: depth, normal and colour images (no counterpart in the reference),
+ *      csrc/tsdf_raycast.hip; tests/tsdf_raycast_restatement.py restates it serially ----
+ *
+ * gs_tsdf_raycast: k frames of h x w pixels through the lattice above (tsdf, weight f32 [nx,ny,nz], colors f32
+ *   [3,nx,ny,nz] or NULL).  c2w f32 [k,3,4] camera-to-world matrices, rows (r0 r1 r2 o).  fx, fy != 0, voxel > 0,
+ *   0 <= near < far (far may be +inf), 0 < step_voxels <= 1, sizes in [2, 1024], h, w >= 1, k >= 0 (0: nothing is
+ *   launched); anything else returns GS_ERR_INVALID_ARG and launches nothing.  Outputs depth f32 [k,h,w], normal f32
+ *   [k,h,w,3], color f32 [k,h,w,3] or NULL (needs colors); every pixel of them is written.  Per pixel (iu, iv), in fp32,
+ *   one rounding per operation, no fma; a MISS writes depth = 0, normal = 0, colour = 0:
+ *
+ *     dx = (float(iu) - cx) / fx ; dy = (float(iv) - cy) / fy          (the direction (dx, dy, 1) is not normalised:
+ *                                                                        t below is depth along the optical axis)
+ *     dw = (r0 * dx + r1 * dy) + r2                                     (per row of c2w)
+ *     og = (o - lo) / voxel ; dg = dw / voxel                           (per axis; index space, g(t) = og + t * dg)
+ *     MISS unless og and dg are finite on every axis
+ *     dt = (step_voxels * voxel) / sqrtf((dw.x * dw.x + dw.y * dw.y) + dw.z * dw.z) ; MISS unless 0 < dt < inf
+ *     t0 = near ; t1 = far ; per axis with top = float(n - 1):
+ *       dg == 0: MISS unless 0 <= og <= top                             (the axis constrains nothing otherwise)
+ *       else   : ta = (0 - og) / dg ; tb = (top - og) / dg ; t0 = max(t0, min(ta, tb)) ; t1 = min(t1, max(ta, tb))
+ *     (og, dg finite and dg != 0: ta and tb are never NaN, and no product 0 * inf is ever formed.)
+ *     for i = 0 .. GS_TSDF_RAY_STEPS: t_i = t0 + float(i) * dt ; stop (MISS) unless t_i < t1
+ *       sample(t): g = og + t * dg (per axis) ; a = floorf(g) ; valid iff 0 <= a < top on every axis (compared as
+ *         floats) and weight >= min_weight at all eight corners a + {0,1}^3 ; fr = g - a ;
+ *         value = trilinear tsdf, lerp(p, q, s) = p + s * (q - p) along z (four), then y (two), then x (one).
+ *       HIT at the first i >= 1 with sample(t_{i-1}) and sample(t_i) valid, f_{i-1} >= 0 and f_i < 0:
+ *         depth = t* = t_{i-1} + dt * (f_{i-1} / (f_{i-1} - f_i)).  Later crossings, back-face ones included, are never
+ *         looked at; a ray that only crosses from negative to positive misses.
+ *     GS_TSDF_RAY_STEPS = ceil((nx + ny + nz) / step_voxels) + 2, in double from the float step_voxels.  A step moves g
+ *       by step_voxels index units and no chord of the box is longer than nx + ny + nz of them, so the bound never
+ *       causes a miss; it is the loop's own bound, so a lane ends whatever the pose holds.  It must not exceed 2^24
+ *       (float(i) is exact): a smaller step_voxels is refused.
+ *     at the hit: the cell of g(t*), valid as above or else MISS (depth too).  With v[x][y][z] its corners and
+ *       (sx, sy, sz) = fr, the gradient of the trilinear interpolant, each component a difference of two bilinear
+ *       values, every lerp as above:
+ *         n.x = yx(1) - yx(0), yx(b) = lerp over y of the two z-lerps of face x = b        (lerps z, then y)
+ *         n.y = zx(1) - zx(0), zx(b) = lerp over x of the two z-lerps of face y = b        (lerps z, then x)
+ *         n.z = yx'(1) - yx'(0), yx'(b) = lerp over x of the two y-lerps of face z = b     (lerps y, then x)
+ *       len = sqrtf((n.x * n.x + n.y * n.y) + n.z * n.z) ; normal = n / len per component, 0 where !(len > 0): world
+ *       frame, toward free space (increasing tsdf).  colour = trilinear colors per channel, lerps z, y, x.
+ *     depth > 0 marks a hit (t* = 0 needs the camera centre on the surface at near = 0 and reads as a miss).
+ *
+ *   flags: NULL, or gs_tsdf_brick_flags' bytes of the SAME tsdf: a sample whose cell lies in a brick with a zero byte
+ *   is not evaluated when reached as t_i (it is evaluated when a later sample needs it as t_{i-1}).  Such a cell's
+ *   corners are all >= 0 and a chain of lerps p + fl(s * fl(q - p)), 0 <= s < 1, of non-negative values is never
+ *   negative (rounding is monotone: fl(q - p) >= -p, so fl(s * ...) >= -p), so that sample cannot satisfy f_i < 0:
+ *   outputs with and without flags are equal bit for bit.
+ * gs_tsdf_brick_flags: flags u8 [bx,by,bz], b = ceil((n - 1) / 8) per axis (gs_tsdf_brick_flags_bytes gives the product,
+ *   0 for sizes outside [2, 1024]): byte (i,j,k) = 1 if tsdf < 0 at any lattice point of [8i, min(8i + 8, nx - 1)] x
+ *   [8j, ..] x [8k, ..] -- the corners of the 8 x 8 x 8 cells of that brick -- else 0.                                  */
+size_t gs_tsdf_brick_flags_bytes(int nx, int ny, int nz);
+int gs_tsdf_brick_flags(const float* tsdf, int nx, int ny, int nz, unsigned char* flags, gs_stream_t stream);
+int gs_tsdf_raycast(const float* tsdf, const float* weight, const float* colors, int nx, int ny, int nz,
+                    const unsigned char* flags, const float* c2w, int k, int h, int w, float fx, float fy, float cx,
+                    float cy, float lo_x, float lo_y, float lo_z, float voxel, float near, float far, float step_voxels,
+                    float min_weight, float* depth, float* normal, float* color, gs_stream_t stream);
+
 /* ---- frame preprocessing of the dataset readers (src/datasets.py:96-143, 565-605), csrc/frame_prep.hip ----
  *
  * Semantics: tests/frame_prep_restatement.py, bit for bit (cv2.remap / cv2.resize INTER_LINEAR on 8-bit data,
