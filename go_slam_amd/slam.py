@@ -194,7 +194,9 @@ class SLAM:
         it, and the final mesh.  With cfg["tsdf"]["enable"] also mesh/tsdf_mesh.ply, the keyframe depth fused into a TSDF
         (tsdf.fuse_from_config; this one also under only_tracking), and with cfg["tsdf"]["eval_depth"]["enable"] (keys
         enable, every, save_images) metrics_tsdf_depth.txt: that volume raycast at the estimated poses against the sensor
-        depth, the means under `tsdf_*` keys of the returned statistics.  With cfg["render_eval"]["enable"] (keys enable, every,
+        depth, the means under `tsdf_*` keys of the returned statistics, and with cfg["tsdf"]["esdf"]["enable"]
+        metrics_tsdf_clearance.txt, the clearance of the estimated camera centres in that volume's distance field, and
+        with its `slice` key map/occupancy.pgm and .yaml (tsdf.fuse_from_config).  With cfg["render_eval"]["enable"] (keys enable, every,
         save_images) and a map, also metrics_render.txt: PSNR, SSIM and depth L1 of the map's renderings against the input
         frames (neus/render_eval.py), their means under `render_*` keys of the returned statistics.  Returns the
         statistics (an empty dict without ground truth and without that step)."""

@@ -10,6 +10,12 @@ csrc/tsdf_raycast.hip looks at the volume from a camera: `TSDFVolume.raycast` ma
 zero crossing and returns depth, normal and colour images, and `eval_tsdf_depth` compares those depth images with the
 sensor's at the end of a run (metrics_tsdf_depth.txt).  tests/tsdf_raycast_restatement.py restates the march (DESIGN.md
 section 22).
+
+csrc/esdf.hip answers what a robot asks of the map: `TSDFVolume.esdf` turns the volume into an `ESDF`, the exact
+Euclidean distance to the nearest surface lattice point at every lattice point, `ESDF.query` interpolates it and its
+gradient at world points, `ESDF.occupancy_slice` / `save_map` flatten a slab into a map_server occupancy map, and
+`trajectory_clearance` reports how close the estimated camera centres come to the fused surfaces
+(metrics_tsdf_clearance.txt).  tests/esdf_restatement.py restates the field.
 """
 import math
 import os
@@ -232,6 +238,228 @@ class TSDFVolume:
         mesh.vertices = np.ascontiguousarray(mesh.vertices * self.voxel + self.lo[None, :])
         return mesh
 
+    @torch.no_grad()
+    def esdf(self, max_distance=None, min_weight=1.0):
+        """The Euclidean distance field of the volume as it is now (gs_esdf_build): an `ESDF` snapshot.  Distances are
+        exact up to `max_distance` metres, R = ceil(max_distance / voxel) voxels in [1, 1023], and capped there; None
+        means R = 1023, which is exact and unbounded on any permitted lattice.  A point counts as seen with weight >=
+        `min_weight`.  Enqueues on the current stream, reads nothing back and leaves the volume untouched.  ValueError
+        for a bad max_distance or min_weight, before the device is touched."""
+        what = "TSDFVolume.esdf"
+        if max_distance is None:
+            radius = ESDF_MAX_RADIUS
+        else:
+            max_distance = float(max_distance)
+            if not (max_distance > 0 and math.isfinite(max_distance)):
+                raise ValueError(f"{what}: max_distance must be positive and finite (got {max_distance})")
+            radius = int(math.ceil(max_distance / self.voxel))
+            if not 1 <= radius <= ESDF_MAX_RADIUS:
+                raise ValueError(f"{what}: max_distance {max_distance} is {radius} voxels of {self.voxel} m "
+                                 f"(at most {ESDF_MAX_RADIUS}); pass None for an unbounded field")
+        min_weight = float(min_weight)
+        if math.isnan(min_weight):
+            raise ValueError(f"{what}: min_weight is NaN")
+        dev = self.device
+        state = torch.empty(self.dims, dtype=torch.uint8, device=dev)
+        d2 = torch.empty(self.dims, dtype=torch.int32, device=dev)
+        dist = torch.empty(self.dims, dtype=torch.float32, device=dev)
+        nx, ny, nz = self.dims
+        with torch.cuda.device(dev):
+            rc = _lib.lib().gs_esdf_build(_lib.ptr(self.tsdf), _lib.ptr(self.weight), nx, ny, nz, min_weight, radius,
+                                          self.voxel, _lib.ptr(state), _lib.ptr(d2), _lib.ptr(dist), _lib.stream_ptr(dev))
+        _lib.check(rc, what)
+        return ESDF(state, d2, dist, self.lo, self.voxel, self.dims, radius)
+
+
+ESDF_MAX_RADIUS = MAX_POINTS - 1     # voxels: no two points of a permitted lattice are further apart along an axis
+MAP_FREE, MAP_OCCUPIED, MAP_UNKNOWN = 254, 0, 205      # the trinary values of a ROS map_server PGM
+
+
+class ESDF:
+    """A snapshot of a TSDFVolume's distance field (TSDFVolume.esdf); it does not refer back to the volume.  On the
+    volume's lattice (`lo`, `voxel`, `dims`): `.state` uint8 (0 unknown, 1 free, 2 solid), `.d2` int32, the squared
+    distance in voxels to the nearest site (a lattice point next to a sign change; 0x7fffffff beyond `radius_voxels`),
+    `.dist` float32 in metres, negative inside solid, +-radius_voxels * voxel beyond the band."""
+
+    def __init__(self, state, d2, dist, lo, voxel, dims, radius_voxels):
+        self.state, self.d2, self.dist = state, d2, dist
+        self.lo = np.array(lo, dtype=np.float64)
+        self.voxel = float(voxel)
+        self.dims = tuple(int(n) for n in dims)
+        self.radius_voxels = int(radius_voxels)
+        self.device = dist.device
+
+    @torch.no_grad()
+    def query(self, points):
+        """The field at world points [N,3] (gs_esdf_query): {"dist": float32 [N], the trilinear interpolant, "grad":
+        float32 [N,3], its analytic gradient (not normalised; toward free space), "valid": bool [N], the point lies in
+        a cell of the lattice, "known": bool [N], all eight corners of that cell were seen}.  Invalid points hold
+        zeros.  Enqueues on the current stream; nothing is read back."""
+        points = torch.as_tensor(points)
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError(f"ESDF.query: points must be [N,3] (got {list(points.shape)})")
+        dev = self.device
+        points = points.to(device=dev, dtype=torch.float32).contiguous()
+        N = int(points.shape[0])
+        dist = torch.empty(N, dtype=torch.float32, device=dev)
+        grad = torch.empty(N, 3, dtype=torch.float32, device=dev)
+        flags = torch.empty(N, dtype=torch.uint8, device=dev)
+        if N > 0:
+            nx, ny, nz = self.dims
+            with torch.cuda.device(dev):
+                rc = _lib.lib().gs_esdf_query(_lib.ptr(self.dist), _lib.ptr(self.state), nx, ny, nz, float(self.lo[0]),
+                                              float(self.lo[1]), float(self.lo[2]), self.voxel, _lib.ptr(points), N,
+                                              _lib.ptr(dist), _lib.ptr(grad), _lib.ptr(flags), _lib.stream_ptr(dev))
+            _lib.check(rc, "ESDF.query")
+        return {"dist": dist, "grad": grad, "valid": (flags & 1) != 0, "known": (flags & 2) != 0}
+
+    def slice_arguments(self, up_axis, height, robot_radius=0.0, known_fraction=0.5):
+        """(up_axis, k0, k1, occ_d2, min_known) of gs_esdf_slice for `occupancy_slice`'s arguments, or ValueError."""
+        what = "ESDF.occupancy_slice"
+        if isinstance(up_axis, bool) or not isinstance(up_axis, (int, np.integer)) or not 0 <= int(up_axis) <= 2:
+            raise ValueError(f"{what}: up_axis must be 0, 1 or 2 (got {up_axis!r})")
+        a = int(up_axis)
+        try:
+            h0, h1 = (float(h) for h in height)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: height must be (h0, h1) in metres (got {height!r})") from None
+        robot_radius, known_fraction = float(robot_radius), float(known_fraction)
+        if math.isnan(h0) or math.isnan(h1):
+            raise ValueError(f"{what}: height {height!r} holds NaN")
+        top = self.dims[a] - 1
+        k0 = 0 if h0 == -math.inf else int(max(math.ceil(min((h0 - self.lo[a]) / self.voxel, top + 1.0)), 0))
+        k1 = top if h1 == math.inf else int(min(math.floor(max((h1 - self.lo[a]) / self.voxel, -1.0)), top))
+        if k0 > k1:
+            raise ValueError(f"{what}: no lattice layer of axis {a} lies in [{h0}, {h1}] m (the axis spans "
+                             f"[{self.lo[a]}, {self.lo[a] + top * self.voxel}] in steps of {self.voxel})")
+        if not 0 <= robot_radius <= self.radius_voxels * self.voxel:
+            raise ValueError(f"{what}: robot_radius {robot_radius} m outside [0, {self.radius_voxels * self.voxel}], "
+                             "the band of this field (build it with a larger max_distance)")
+        if not 0 <= known_fraction <= 1:
+            raise ValueError(f"{what}: known_fraction must lie in [0, 1] (got {known_fraction})")
+        occ_d2 = int(math.floor((robot_radius / self.voxel) ** 2))
+        min_known = int(math.ceil(known_fraction * (k1 - k0 + 1)))
+        return a, k0, k1, occ_d2, min_known
+
+    @torch.no_grad()
+    def occupancy_slice(self, up_axis, height, robot_radius=0.0, known_fraction=0.5):
+        """The 2-D map of the slab of lattice layers k along `up_axis` with height[0] <= lo + k * voxel <= height[1]
+        (gs_esdf_slice).  The two other axes, in increasing order, index the images [n_u, n_v].  A column is occupied
+        (cells 0) when a point of it is solid or within `robot_radius` of a site, else free (254) when at least
+        `known_fraction` of its points were seen, else unknown (205).  -> {"cells": uint8 [n_u,n_v], "clearance":
+        float32 [n_u,n_v], the smallest dist of the column in metres, "origin": (x, y), the corner of cell (0, 0) along
+        the two image axes (its lattice point minus half a voxel: map_server's origin), "resolution": the voxel, "axes":
+        (u, v)}, images on the field's device.  ValueError for an empty range or a radius beyond the field's band."""
+        a, k0, k1, occ_d2, min_known = self.slice_arguments(up_axis, height, robot_radius, known_fraction)
+        u, v = [ax for ax in range(3) if ax != a]
+        dev = self.device
+        cells = torch.empty((self.dims[u], self.dims[v]), dtype=torch.uint8, device=dev)
+        clearance = torch.empty((self.dims[u], self.dims[v]), dtype=torch.float32, device=dev)
+        nx, ny, nz = self.dims
+        with torch.cuda.device(dev):
+            rc = _lib.lib().gs_esdf_slice(_lib.ptr(self.state), _lib.ptr(self.d2), _lib.ptr(self.dist), nx, ny, nz, a, k0,
+                                          k1, occ_d2, min_known, _lib.ptr(cells), _lib.ptr(clearance),
+                                          _lib.stream_ptr(dev))
+        _lib.check(rc, "ESDF.occupancy_slice")
+        return {"cells": cells, "clearance": clearance, "resolution": self.voxel, "axes": (u, v),
+                "origin": (float(self.lo[u] - 0.5 * self.voxel), float(self.lo[v] - 0.5 * self.voxel))}
+
+    def save_map(self, directory, up_axis, height, robot_radius=0.0, known_fraction=0.5):
+        """`occupancy_slice` written as `directory`/occupancy.pgm and occupancy.yaml (save_map); returns the slice."""
+        grid = self.occupancy_slice(up_axis, height, robot_radius, known_fraction)
+        save_map(directory, grid)
+        return grid
+
+
+def save_map(directory, grid):
+    """Write `ESDF.occupancy_slice`'s dict as a ROS map_server map: occupancy.pgm (binary P5, n_u wide, n_v high; file
+    row r is image index v = n_v - 1 - r, the column is u, so the picture has u to the right and v upward) and
+    occupancy.yaml with the keys image, resolution, origin [x, y, 0.0], negate 0, occupied_thresh 0.65, free_thresh 0.196.
+    Numbers are written with repr(): `load_map` gives them back bit for bit."""
+    cells = grid["cells"]
+    cells = cells.detach().cpu().numpy() if isinstance(cells, torch.Tensor) else np.asarray(cells)
+    if cells.ndim != 2 or cells.dtype != np.uint8:
+        raise ValueError(f"save_map: cells must be uint8 [n_u,n_v] (got {cells.dtype} {list(cells.shape)})")
+    n_u, n_v = cells.shape
+    os.makedirs(directory, exist_ok=True)
+    with open(os.path.join(directory, "occupancy.pgm"), "wb") as fh:
+        fh.write(f"P5\n{n_u} {n_v}\n255\n".encode("ascii"))
+        fh.write(np.ascontiguousarray(cells[:, ::-1].T).tobytes())
+    x, y = (float(c) for c in grid["origin"])
+    with open(os.path.join(directory, "occupancy.yaml"), "w") as fh:
+        fh.write(f"image: occupancy.pgm\nresolution: {float(grid['resolution'])!r}\norigin: [{x!r}, {y!r}, 0.0]\n"
+                 "negate: 0\noccupied_thresh: 0.65\nfree_thresh: 0.196\n")
+
+
+def load_map(directory):
+    """save_map's inverse: {"cells": uint8 [n_u,n_v] (host), "origin": (x, y), "resolution"}."""
+    keys = {}
+    with open(os.path.join(directory, "occupancy.yaml")) as fh:
+        for line in fh:
+            name, _, value = line.partition(":")
+            keys[name.strip()] = value.strip()
+    origin = [float(c) for c in keys["origin"].strip("[]").split(",")]
+    with open(os.path.join(directory, keys["image"]), "rb") as fh:
+        data = fh.read()
+    magic, size, maxval, pixels = data.split(b"\n", 3)
+    n_u, n_v = (int(s) for s in size.split())
+    if magic != b"P5" or maxval != b"255" or len(pixels) != n_u * n_v:
+        raise ValueError(f"load_map: {directory}/{keys['image']} is not an 8-bit binary PGM of the size it names")
+    rows = np.frombuffer(pixels, dtype=np.uint8).reshape(n_v, n_u)
+    return {"cells": np.ascontiguousarray(rows.T[:, ::-1]), "origin": (origin[0], origin[1]),
+            "resolution": float(keys["resolution"])}
+
+
+CLEARANCE_REPORT_ORDER = ("clearance_min_m", "clearance_mean_m", "n_inside", "n_unknown", "n_poses")
+
+
+def clearance_text(result):
+    """The text of metrics_tsdf_clearance.txt: two header lines, then `name<TAB>value` per reported value, written
+    with repr() so that reading the file gives back the numbers bit for bit."""
+    lines = ["Clearance of the estimated camera centres in the fused TSDF volume's distance field: the distance [m] to "
+             "the nearest surface, over the centres that lie in a cell whose eight corners were seen",
+             "(n_inside: such centres with a negative distance, inside fused solid; n_unknown: centres outside the "
+             "lattice or in a cell with a never-seen corner; nan without any usable centre)"]
+    lines += [f"{k}\t{result[k]!r}" for k in CLEARANCE_REPORT_ORDER]
+    return "\n".join(lines) + "\n"
+
+
+def parse_clearance(text):
+    """clearance_text's inverse: the reported dict."""
+    lines = text.splitlines()
+    if len(lines) != 2 + len(CLEARANCE_REPORT_ORDER) or not lines[0].startswith("Clearance of the estimated camera"):
+        raise ValueError("not a metrics_tsdf_clearance.txt")
+    result = {}
+    for key, line in zip(CLEARANCE_REPORT_ORDER, lines[2:]):
+        name, value = line.split("\t")
+        if name != key:
+            raise ValueError(f"metrics_tsdf_clearance.txt: expected {key}, found {name}")
+        result[key] = int(value) if key.startswith("n_") else float(value)
+    return result
+
+
+@torch.no_grad()
+def trajectory_clearance(esdf, c2w_list, out_path=None):
+    """Query `esdf` at the camera centres of the camera-to-world poses c2w_list ([4,4] or [3,4] each, the volume's
+    frame).  -> {"clearance_min_m", "clearance_mean_m": over the valid and known centres (nan without one), "n_inside":
+    known centres with dist < 0, "n_unknown": invalid or not known ones, "n_poses"}; the sums are fp64 on the device and
+    read back in one read.  With `out_path` also writes clearance_text() there."""
+    n = len(c2w_list)
+    centres = torch.stack([torch.as_tensor(c)[:3, 3] for c in c2w_list]).to(torch.float32) if n else torch.zeros(0, 3)
+    res = esdf.query(centres)
+    ok = res["valid"] & res["known"]
+    d = res["dist"].double()
+    inf = torch.full_like(d, math.inf)
+    sums = torch.stack([torch.where(ok, d, inf).min() if n else inf.sum(), (d * ok).sum(), ok.sum().double(),
+                        (ok & (res["dist"] < 0)).sum().double()]).cpu().tolist()             # the one read
+    n_ok = int(sums[2])
+    result = {"clearance_min_m": sums[0] if n_ok else math.nan, "clearance_mean_m": sums[1] / n_ok if n_ok else math.nan,
+              "n_inside": int(sums[3]), "n_unknown": n - n_ok, "n_poses": n}
+    if out_path is not None:
+        with open(out_path, "w") as fh:
+            fh.write(clearance_text(result))
+    return result
+
 
 def _inverse(disp):
     return torch.where(disp > 0, 1.0 / disp, torch.zeros_like(disp))
@@ -397,7 +625,12 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
     into {output}/metrics_tsdf_mesh.txt.  With cfg["tsdf"]["eval_depth"]["enable"] (keys enable, every, save_images;
     absent by default) also raycast the fused volume at the poses `c2w_list` of the frames of `stream` and compare with
     their sensor depth (eval_tsdf_depth) into {output}/metrics_tsdf_depth.txt, the means under `tsdf_*` keys of the dict
-    `stats`.  Returns the Mesh, or None when the key is absent or disabled."""
+    `stats`.  With cfg["tsdf"]["esdf"]["enable"] (keys enable, max_distance, save_volume, slice; absent by default)
+    also build the fused volume's distance field and write the clearance of the camera centres `c2w_list` into
+    {output}/metrics_tsdf_clearance.txt (trajectory_clearance; `tsdf_clearance_min_m`, `tsdf_clearance_inside` and
+    `tsdf_clearance_unknown` in `stats`), with save_volume {output}/mesh/tsdf_esdf.npz (dist, state, lo, voxel), and with
+    slice = {up_axis, height, robot_radius, known_fraction} the map {output}/map/occupancy.pgm and occupancy.yaml
+    (ESDF.save_map).  Returns the Mesh, or None when the key is absent or disabled."""
     opt = slam.cfg.get("tsdf") or {}
     if not opt.get("enable", False):
         return None
@@ -418,6 +651,23 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
         if stats is not None:
             stats.update({f"tsdf_{k}": res[k] for k in DEPTH_REPORT_ORDER})
         print("TSDF depth: " + ", ".join(f"{k} {res[k]!r}" for k in DEPTH_REPORT_ORDER))
+    ed = opt.get("esdf") or {}
+    if ed.get("enable", False):
+        if c2w_list is None:
+            raise ValueError("fuse_from_config: tsdf.esdf needs the run's camera-to-world poses")
+        field = vol.esdf(ed.get("max_distance"), min_weight=min_weight)
+        res = trajectory_clearance(field, c2w_list, out_path=f"{slam.output}/metrics_tsdf_clearance.txt")
+        if stats is not None:
+            stats.update(tsdf_clearance_min_m=res["clearance_min_m"], tsdf_clearance_inside=res["n_inside"],
+                         tsdf_clearance_unknown=res["n_unknown"])
+        print("TSDF clearance: " + ", ".join(f"{k} {res[k]!r}" for k in CLEARANCE_REPORT_ORDER))
+        if ed.get("save_volume", False):
+            np.savez(f"{slam.output}/mesh/tsdf_esdf.npz", dist=field.dist.cpu().numpy(), state=field.state.cpu().numpy(),
+                     lo=field.lo, voxel=field.voxel)
+        sl = ed.get("slice")
+        if sl:
+            field.save_map(f"{slam.output}/map", sl["up_axis"], sl["height"], sl.get("robot_radius", 0.0),
+                           sl.get("known_fraction", 0.5))
     meshing = slam.cfg.get("meshing") or {}
     gt_path = meshing.get("gt_mesh_path") or ""
     if meshing.get("eval_rec") and gt_path.find(".ply") > -1 and os.path.exists(gt_path) and len(mesh.faces) > 0:

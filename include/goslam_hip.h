@@ -297,6 +297,55 @@ int gs_tsdf_raycast(const float* tsdf, const float* weight, const float* colors,
                     float cy, float lo_x, float lo_y, float lo_z, float voxel, float near, float far, float step_voxels,
                     float min_weight, float* depth, float* normal, float* color, gs_stream_t stream);
 
+/* ---- Euclidean distance field and 2-D occupancy map of that TSDF lattice (no counterpart in the reference),
+ *      csrc/esdf.hip; tests/esdf_restatement.py restates it serially ----
+ *
+ * The lattice is the one above: nx x ny x nz, z contiguous, each size in [2, 1024], 64-bit offsets.  Bad sizes, radii,
+ * ranges or NULL pointers return GS_ERR_INVALID_ARG before anything is launched.
+ *
+ * gs_esdf_build: tsdf, weight f32 [nx,ny,nz] (read only), radius R in [1, 1023] voxels, voxel > 0 finite, min_weight
+ *   not NaN.  Outputs state u8, d2 i32, dist f32, all [nx,ny,nz], every element written.
+ *     state = 0 (unknown) when !(weight >= min_weight)  (a NaN weight is unknown)
+ *             else 2 (solid) when tsdf < 0, else 1 (free; a NaN tsdf is free)
+ *     site  : state != 0 and some 6-neighbour inside the lattice has state != 0 and another state (both ends of a sign
+ *             change are sites)
+ *     d2    : the squared lattice distance to the nearest site, band-limited.  Start value 0 at sites, INF = 0x3fffffff
+ *             elsewhere; three passes, along z, then y, then x, each per line of n values
+ *               out[i] = min over |k| <= R, 0 <= i + k < n of in[i + k] + k * k
+ *             and after the third every value > R * R becomes FAR = 0x7fffffff.  (INF + 1023^2 < 2^31.)
+ *             A value <= R * R is the true unbounded squared distance: the nearest site then has every axis offset <= R,
+ *             and the three windowed minima are the separable form of the minimum over that cube.  The kernels run
+ *               best = in[i] ; for (k = 1; k <= R && k * k < best; ++k) best = min(best, in[i-k] + k*k, in[i+k] + k*k)
+ *             which is the same minimum (a term with k * k >= best cannot lower best) and ends after at most R steps.
+ *     dist  = sign * (voxel * sqrtf((float)d2)) in metres, sign = -1 where state == 2, else +1; a FAR point gets
+ *             sign * (voxel * (float)R).  d2 <= 3 * 1023^2 < 2^24: the conversion is exact; one sqrtf, one multiply.
+ *   dist serves as the int32 ping-pong buffer of the passes; there is no other workspace.
+ * gs_esdf_query: points f32 [n,3] in world coordinates -> out_dist f32 [n], out_grad f32 [n,3], out_flags u8 [n], every
+ *   element written; n == 0 launches nothing.  Per point and axis g = (p - lo) / voxel, a = floorf(g).  Bit 0 of flags
+ *   (valid): 0 <= a < float(n - 1) on every axis, compared as floats before the cast (NaN and +-inf fail).  An invalid
+ *   point writes zeros and flags = 0.  Otherwise, with v[x][y][z] the cell's eight corners of dist, (sx, sy, sz) = g - a
+ *   and lerp(p, q, s) = p + s * (q - p):
+ *     zXY = lerp(v[X][Y][0], v[X][Y][1], sz) ; yXZ = lerp(v[X][0][Z], v[X][1][Z], sy)
+ *     x0 = lerp(z00, z01, sy) ; x1 = lerp(z10, z11, sy) ; out_dist = lerp(x0, x1, sx)       (lerps z, then y, then x)
+ *     out_grad.x = (x1 - x0) / voxel                                                        (lerps z, then y)
+ *     out_grad.y = (lerp(z01, z11, sx) - lerp(z00, z10, sx)) / voxel                        (lerps z, then x)
+ *     out_grad.z = (lerp(y01, y11, sx) - lerp(y00, y10, sx)) / voxel                        (lerps y, then x)
+ *   the analytic gradient of the interpolant, not normalised.  Bit 1 of flags (known): all eight corners have
+ *   state != 0.
+ * gs_esdf_slice: the map of the slab of layers [k0, k1] (inclusive, 0 <= k0 <= k1 < n) along up_axis in {0, 1, 2};
+ *   occ_d2 >= 0, min_known >= 0.  The two other axes, in increasing axis order, index the images cells u8 [n_u,n_v] and
+ *   clearance f32 [n_u,n_v].  Per column, layers in increasing order:
+ *     occupied = any(state == 2 || d2 <= occ_d2) ; n_known = count(state != 0)
+ *     cells = 0 when occupied, else 254 when n_known >= min_known, else 205    (the trinary values of a map_server PGM)
+ *     clearance = the minimum of dist: c = dist[k0], then c = dist[k] where dist[k] < c.                            */
+int gs_esdf_build(const float* tsdf, const float* weight, int nx, int ny, int nz, float min_weight, int radius,
+                  float voxel, unsigned char* state, int* d2, float* dist, gs_stream_t stream);
+int gs_esdf_query(const float* dist, const unsigned char* state, int nx, int ny, int nz, float lo_x, float lo_y,
+                  float lo_z, float voxel, const float* points, int n, float* out_dist, float* out_grad,
+                  unsigned char* out_flags, gs_stream_t stream);
+int gs_esdf_slice(const unsigned char* state, const int* d2, const float* dist, int nx, int ny, int nz, int up_axis,
+                  int k0, int k1, int occ_d2, int min_known, unsigned char* cells, float* clearance, gs_stream_t stream);
+
 /* ---- frame preprocessing of the dataset readers (src/datasets.py:96-143, 565-605), csrc/frame_prep.hip ----
  *
  * Semantics: tests/frame_prep_restatement.py, bit for bit (cv2.remap / cv2.resize INTER_LINEAR on 8-bit data,
