@@ -70,6 +70,11 @@ struct GsLdsLimit {
 static inline int gs_cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline size_t gs_align(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
+// torch's clamp(lo, hi): a NaN stays a NaN (fminf(fmaxf(v, lo), hi) would turn it into lo)
+__device__ __forceinline__ float gs_clamp_keep_nan(float v, float lo, float hi) {
+  return v < lo ? lo : (v > hi ? hi : v);
+}
+
 // ---------------------------------------------------------------- SE3 on the device ----
 // Pose layout [tx,ty,tz,qx,qy,qz,qw] (world->camera), see SURVEY App. A.  All of these are
 // written so that, compiled with -ffp-contract=off, they round exactly like the op-by-op fp32

@@ -459,10 +459,10 @@ __global__ __launch_bounds__(256) void motion_features_kernel(const float2* __re
   const float2 c = coords1[t], tg = target[t];
   typedef _Float16 half4m __attribute__((ext_vector_type(4)));
   half4m o;
-  o[0] = (_Float16)fminf(fmaxf(c.x - gx, -64.0f), 64.0f);
-  o[1] = (_Float16)fminf(fmaxf(c.y - gy, -64.0f), 64.0f);
-  o[2] = (_Float16)fminf(fmaxf(tg.x - c.x, -64.0f), 64.0f);
-  o[3] = (_Float16)fminf(fmaxf(tg.y - c.y, -64.0f), 64.0f);
+  o[0] = (_Float16)gs_clamp_keep_nan(c.x - gx, -64.0f, 64.0f);
+  o[1] = (_Float16)gs_clamp_keep_nan(c.y - gy, -64.0f, 64.0f);
+  o[2] = (_Float16)gs_clamp_keep_nan(tg.x - c.x, -64.0f, 64.0f);
+  o[3] = (_Float16)gs_clamp_keep_nan(tg.y - c.y, -64.0f, 64.0f);
   reinterpret_cast<half4m*>(out)[t] = o;
 }
 

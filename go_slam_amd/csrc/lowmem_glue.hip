@@ -44,10 +44,10 @@ __global__ __launch_bounds__(256) void lowmem_gather_kernel(const float2* __rest
     c_out[(size_t)r * hw + p] = c;
     const float gx = (float)(p % w), gy = (float)(p / w);
     half4g o;
-    o[0] = (_Float16)fminf(fmaxf(c.x - gx, -64.0f), 64.0f);
-    o[1] = (_Float16)fminf(fmaxf(c.y - gy, -64.0f), 64.0f);
-    o[2] = (_Float16)fminf(fmaxf(tg.x - c.x, -64.0f), 64.0f);
-    o[3] = (_Float16)fminf(fmaxf(tg.y - c.y, -64.0f), 64.0f);
+    o[0] = (_Float16)gs_clamp_keep_nan(c.x - gx, -64.0f, 64.0f);
+    o[1] = (_Float16)gs_clamp_keep_nan(c.y - gy, -64.0f, 64.0f);
+    o[2] = (_Float16)gs_clamp_keep_nan(tg.x - c.x, -64.0f, 64.0f);
+    o[3] = (_Float16)gs_clamp_keep_nan(tg.y - c.y, -64.0f, 64.0f);
     reinterpret_cast<half4g*>(motion)[(size_t)r * hw + p] = o;
   }
 #pragma unroll
