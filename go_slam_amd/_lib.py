@@ -57,6 +57,9 @@ SIGNATURES = {
     "gs_tsdf_batch": (c_int, []),
     "gs_tsdf_integrate": (c_int, [_P] * 3 + [c_int] * 3 + [_P] * 4 + [c_int] * 3 + [c_float] * 10 + [_P]),
     "gs_tsdf_vertex_attr": (c_int, [_P, c_int, _P, _P, c_int, c_int, c_int, c_float, _P, _P, _P]),
+    "gs_tsdf_accumulate": (c_int, [_P] * 4 + [c_int] * 3 + [_P] * 5 + [c_int] * 3 + [c_float] * 9 + [_P]),
+    "gs_tsdf_resolve": (c_int, [_P] * 4 + [c_int] * 3 + [_P] * 4),
+    "gs_tsdf_frame_change": (c_int, [_P] * 4 + [c_int] * 3 + [c_float, _P, _P]),
     "gs_tsdf_brick_flags_bytes": (c_size_t, [c_int] * 3),
     "gs_tsdf_brick_flags": (c_int, [_P, c_int, c_int, c_int, _P, _P]),
     "gs_tsdf_raycast": (c_int, [_P] * 3 + [c_int] * 3 + [_P, _P] + [c_int] * 3 + [c_float] * 12 + [_P] * 4),

@@ -117,6 +117,9 @@ class SLAM:
         self.traj_filler = PoseTrajectoryFiller(net=self.net, video=self.video, device=self.device)
         self.mapper = Mapper(cfg, args, self)
         self.mesher = Mesher(cfg, args, self)
+        from .tsdf_live import live_from_config
+        self.live = live_from_config(self)          # None unless cfg["tsdf"]["live"]["enable"]
+        self.live_mesh_every = int(((cfg.get("tsdf") or {}).get("live") or {}).get("mesh_every", 0))
 
     def update_cam(self, cfg):
         """Intrinsics after the preprocessing of the frames: resize to (H_out + 2 H_edge, W_out + 2 W_edge), then crop
@@ -154,6 +157,9 @@ class SLAM:
           * after a frame that added a keyframe, `multiview_filter()` then `mapper()` -- one round each of the loops of
             `multiview_filtering` (:246-249) and `mapping` (:256-259), which there spin beside the tracker;
           * after every `full_ba_every` new keyframes, `ba()` -- the loop of `optimizing` (:232-235);
+          * with cfg["tsdf"]["live"]["enable"], `live.update()` after a frame that added a keyframe and after every
+            `ba()` -- no counterpart: the running TSDF volume follows the poses (tsdf_live.LiveFusion; also under
+            only_tracking), and with its `mesh_every` > 0 mesh/live/{timestamp:05d}.ply at those timestamps;
           * with make_video, `mesher()` at every 50th timestamp -- `hang_on` and the meshing worker (:220-224, :271-275);
           * after the stream: a last `ba()` (:237-238), one `multiview_filter()`, `post_processing_iters` times
             `mapper(the_end=True)` (:261-264), then the finished flags (:226, :239, :265, :277, :286).
@@ -162,6 +168,7 @@ class SLAM:
         self.num_running_thread[0] += 1
         self.all_trigered += 1
         since_ba = 0
+        live = getattr(self, "live", None)          # (a SLAM assembled without __init__ has none)
         for timestamp, image, depth, intrinsic, gt_pose in stream:
             if self.mode != "rgbd":
                 depth = None
@@ -172,13 +179,22 @@ class SLAM:
                 if not self.only_tracking:
                     self.multiview_filter()
                     self.mapper()
+                if live is not None:
+                    live.update()
                 if since_ba >= self.full_ba_every:
                     self.ba()
                     since_ba = 0
+                    if live is not None:
+                        live.update()
+            if live is not None and self.live_mesh_every > 0 and timestamp % self.live_mesh_every == 0 and timestamp > 0:
+                from .tsdf_live import save_live_mesh
+                save_live_mesh(self, f"{self.output}/mesh/live/{int(timestamp):05d}.ply")
             if self.make_video and not self.only_tracking and timestamp % MESH_EVERY == 0 and timestamp > 0:
                 self.mesher()
         self.tracking_finished += 1
         self.ba()
+        if live is not None:
+            live.update()
         self.optimizing_finished += 1
         if not self.only_tracking:
             self.multiview_filter()
@@ -196,8 +212,10 @@ class SLAM:
         enable, every, save_images) metrics_tsdf_depth.txt: that volume raycast at the estimated poses against the sensor
         depth, the means under `tsdf_*` keys of the returned statistics, and with cfg["tsdf"]["esdf"]["enable"]
         metrics_tsdf_clearance.txt, the clearance of the estimated camera centres in that volume's distance field, and
-        with its `slice` key map/occupancy.pgm and .yaml (tsdf.fuse_from_config).  With cfg["render_eval"]["enable"] (keys enable, every,
-        save_images) and a map, also metrics_render.txt: PSNR, SSIM and depth L1 of the map's renderings against the input
+        with its `slice` key map/occupancy.pgm and .yaml (tsdf.fuse_from_config).  With cfg["tsdf"]["live"]["enable"] the
+        running volume is brought to the final poses (LiveFusion.finish) and meshed into mesh/tsdf_live_mesh.ply, and
+        `tsdf_live_refused` (keyframes re-fused over the run) and `tsdf_live_keyframes` join the statistics.  With
+        cfg["render_eval"]["enable"] (keys enable, every, save_images) and a map, also metrics_render.txt: PSNR, SSIM and depth L1 of the map's renderings against the input
         frames (neus/render_eval.py), their means under `render_*` keys of the returned statistics.  Returns the
         statistics (an empty dict without ground truth and without that step)."""
         os.makedirs(f"{self.output}/checkpoints/", exist_ok=True)
@@ -249,5 +267,10 @@ class SLAM:
         if (self.cfg.get("tsdf") or {}).get("enable", False):     # mesh/tsdf_mesh.ply, also under only_tracking
             from .tsdf import fuse_from_config
             fuse_from_config(self, stream=stream, trans_init=trans_init, c2w_list=estimate_c2w_list, stats=stats)
+        if getattr(self, "live", None) is not None:               # mesh/tsdf_live_mesh.ply, also under only_tracking
+            from .tsdf_live import save_live_mesh
+            self.live.finish()
+            save_live_mesh(self, f"{self.output}/mesh/tsdf_live_mesh.ply")
+            stats.update(tsdf_live_refused=self.live.total["refused"], tsdf_live_keyframes=len(self.live))
         print("Terminate: Done!")
         return stats

@@ -16,6 +16,9 @@ Euclidean distance to the nearest surface lattice point at every lattice point, 
 gradient at world points, `ESDF.occupancy_slice` / `save_map` flatten a slab into a map_server occupancy map, and
 `trajectory_clearance` reports how close the estimated camera centres come to the fused surfaces
 (metrics_tsdf_clearance.txt).  tests/esdf_restatement.py restates the field.
+
+tsdf_live.py keeps such a volume during a run, while the poses still move; it fuses through
+`keyframe_observations`, the rule `fuse_keyframes` applies per chunk.
 """
 import math
 import os
@@ -67,30 +70,35 @@ def _intrinsics4(intrinsics, what):
     return [float(v) for v in intr]
 
 
+def lattice(bound, voxel_size, trunc, what):
+    """(voxel, lo float64 [3], dims, trunc) of the lattice over `bound` ([3,2]: lo, hi per axis): points at
+    lo + idx * voxel, n = ceil((hi - lo) / voxel) + 1 per axis, truncation 4 voxels unless given.  ValueError for a bad
+    bound or voxel, an empty axis or one with more than MAX_POINTS points."""
+    bound = np.asarray(bound.detach().cpu() if isinstance(bound, torch.Tensor) else bound, dtype=np.float64)
+    if bound.shape != (3, 2):
+        raise ValueError(f"{what}: bound must be [3,2] (got {bound.shape})")
+    voxel = float(voxel_size)
+    if not voxel > 0:
+        raise ValueError(f"{what}: voxel_size must be positive (got {voxel_size})")
+    dims = []
+    for axis, name in enumerate("xyz"):
+        n = int(math.ceil((bound[axis, 1] - bound[axis, 0]) / voxel)) + 1
+        if n > MAX_POINTS:
+            raise ValueError(f"{what}: axis {name} needs {n} lattice points at voxel_size {voxel} "
+                             f"(at most {MAX_POINTS}); enlarge voxel_size or shrink the bound")
+        if n < 2:
+            raise ValueError(f"{what}: axis {name} of the bound is empty")
+        dims.append(n)
+    return voxel, bound[:, 0].copy(), tuple(dims), 4.0 * voxel if trunc is None else float(trunc)
+
+
 class TSDFVolume:
     """A dense TSDF over `bound` ([3,2]: lo, hi per axis) with lattice points at lo + idx * voxel_size,
     n = ceil((hi - lo) / voxel_size) + 1 per axis.  `.tsdf` (+1 where nothing was seen) and `.weight` are float32
     [nx,ny,nz], `.colors` float32 [3,nx,ny,nz], on `device`."""
 
     def __init__(self, bound, voxel_size, trunc=None, max_weight=64.0, device=None):
-        bound = np.asarray(bound.detach().cpu() if isinstance(bound, torch.Tensor) else bound, dtype=np.float64)
-        if bound.shape != (3, 2):
-            raise ValueError(f"TSDFVolume: bound must be [3,2] (got {bound.shape})")
-        self.voxel = float(voxel_size)
-        if not self.voxel > 0:
-            raise ValueError(f"TSDFVolume: voxel_size must be positive (got {voxel_size})")
-        self.lo = bound[:, 0].copy()
-        dims = []
-        for axis, name in enumerate("xyz"):
-            n = int(math.ceil((bound[axis, 1] - bound[axis, 0]) / self.voxel)) + 1
-            if n > MAX_POINTS:
-                raise ValueError(f"TSDFVolume: axis {name} needs {n} lattice points at voxel_size {self.voxel} "
-                                 f"(at most {MAX_POINTS}); enlarge voxel_size or shrink the bound")
-            if n < 2:
-                raise ValueError(f"TSDFVolume: axis {name} of the bound is empty")
-            dims.append(n)
-        self.dims = tuple(dims)
-        self.trunc = 4.0 * self.voxel if trunc is None else float(trunc)
+        self.voxel, self.lo, self.dims, self.trunc = lattice(bound, voxel_size, trunc, "TSDFVolume")
         self.max_weight = float(max_weight)
         if not self.trunc > 0 or not self.max_weight >= 1:
             raise ValueError(f"TSDFVolume: trunc {self.trunc} must be positive and max_weight {self.max_weight} >= 1")
@@ -466,6 +474,40 @@ def _inverse(disp):
 
 
 @torch.no_grad()
+def keyframe_observations(video, source, ids, intr, w2w_inv, filter_thresh=0.01, visible_num=2, depth_filter=None):
+    """What `fuse_keyframes` fuses for the keyframes `ids` (int64, host) of one chunk, as its docstring says per source:
+    (depth [k,H,W], w2c [k,7], images [k,3,H,W], mask [k,H,W] or None).  `intr` is intrinsics[0] * 8 on the device,
+    `w2w_inv` SE3(pose_compensate[0]).inv().  `depth_filter`: the count behind the "tracked" mask, droid_backends' by
+    default (tests pass their restatement's).  `tsdf_live.LiveFusion` fuses through the same rule."""
+    if depth_filter is None:
+        from . import droid_backends
+        depth_filter = droid_backends.depth_filter
+    dev = video.disps_up.device
+    poses = video.poses_filtered if source == "filtered" else video.poses
+    ids_d = ids.to(dev)
+    w2c = (SE3(poses[ids_d]) * w2w_inv).data       # the inverse of w2w * SE3(pose).inv(); exact for the identity
+    mask = None
+    if source == "tracked":
+        disps = _rows(video.disps_up, ids)
+        thresh = float(filter_thresh) * torch.ones(ids.numel(), dtype=torch.float32, device=dev)
+        count = depth_filter(video.poses, video.disps_up, intr, ids_d, thresh)
+        mask = ((count >= visible_num) & (disps > 0.01 * disps.mean(dim=[1, 2], keepdim=True))).float()
+        depth = _inverse(disps)
+    elif source == "filtered":
+        depth = _inverse(_rows(video.disps_filtered, ids))
+        mask = _rows(video.mask_filtered, ids)
+    else:
+        depth = _rows(video.depths_gt, ids)
+    return depth, w2c, _rows(video.images, ids), mask
+
+
+def _sensor_needs_rgbd(video, what):
+    if getattr(video, "cfg", None) is not None and video.cfg.get("mode", "rgbd") != "rgbd":
+        raise ValueError(f"{what}: source='sensor' needs rgbd mode (mode is {video.cfg.get('mode')!r}: "
+                         "no sensor depth is stored)")
+
+
+@torch.no_grad()
 def fuse_keyframes(video, bound, voxel_size, source="tracked", index=None, trunc=None, filter_thresh=0.01, visible_num=2,
                    min_weight=1.0):
     """Fuse keyframes of a full-resolution DepthVideo into a TSDFVolume over `bound` and mesh it: (TSDFVolume, Mesh).
@@ -478,13 +520,11 @@ def fuse_keyframes(video, bound, voxel_size, source="tracked", index=None, trunc
     filter_thresh, and disparity > 0.01 x the keyframe's mean.
     source="filtered": disps_filtered, mask_filtered and poses_filtered of keyframes [0, filtered_id); index must be None.
     source="sensor": depths_gt at the tracked poses, unmasked; needs rgbd mode."""
-    from . import droid_backends
     dev = video.disps_up.device
     num = int(video.disps_up.shape[0])
     if source in ("tracked", "sensor"):
-        if source == "sensor" and getattr(video, "cfg", None) is not None and video.cfg.get("mode", "rgbd") != "rgbd":
-            raise ValueError(f"fuse_keyframes: source='sensor' needs rgbd mode (mode is {video.cfg.get('mode')!r}: "
-                             "no sensor depth is stored)")
+        if source == "sensor":
+            _sensor_needs_rgbd(video, "fuse_keyframes")
         idx = _host_index(range(int(video.counter.value)) if index is None else index, num)
     elif source == "filtered":
         if index is not None:
@@ -496,24 +536,10 @@ def fuse_keyframes(video, bound, voxel_size, source="tracked", index=None, trunc
     intr = (video.intrinsics[0] * 8).contiguous()
     intr_host = intr.cpu().tolist()
     w2w_inv = SE3(video.pose_compensate[0].clone().unsqueeze(0)).inv()
-    poses = video.poses_filtered if source == "filtered" else video.poses
     for a in range(0, idx.numel(), CHUNK):
-        ids = idx[a:a + CHUNK]
-        ids_d = ids.to(dev)
-        w2c = (SE3(poses[ids_d]) * w2w_inv).data       # the inverse of w2w * SE3(pose).inv(); exact for the identity
-        mask = None
-        if source == "tracked":
-            disps = _rows(video.disps_up, ids)
-            thresh = float(filter_thresh) * torch.ones(ids.numel(), dtype=torch.float32, device=dev)
-            count = droid_backends.depth_filter(video.poses, video.disps_up, intr, ids_d, thresh)
-            mask = ((count >= visible_num) & (disps > 0.01 * disps.mean(dim=[1, 2], keepdim=True))).float()
-            depth = _inverse(disps)
-        elif source == "filtered":
-            depth = _inverse(_rows(video.disps_filtered, ids))
-            mask = _rows(video.mask_filtered, ids)
-        else:
-            depth = _rows(video.depths_gt, ids)
-        vol.integrate(depth, w2c, intr_host, images=_rows(video.images, ids), mask=mask)
+        depth, w2c, images, mask = keyframe_observations(video, source, idx[a:a + CHUNK], intr, w2w_inv, filter_thresh,
+                                                         visible_num)
+        vol.integrate(depth, w2c, intr_host, images=images, mask=mask)
     return vol, vol.extract_mesh(min_weight)
 
 

@@ -241,6 +241,60 @@ int gs_tsdf_integrate(float* tsdf, float* weight, float* colors, int nx, int ny,
 int gs_tsdf_vertex_attr(const float* vertices, int n_vertices, const float* weight, const float* colors, int nx, int ny,
                         int nz, float min_weight, unsigned char* keep, float* rgb, gs_stream_t stream);
 
+/* ---- reversible TSDF fusion on that lattice: integer sums that an observation can leave again (no counterpart in the
+ *      reference), csrc/tsdf_live.hip; tests/tsdf_live_restatement.py restates it serially ----
+ *
+ * State, all zero in a fresh volume: sum_s i32 [nx,ny,nz], count i32 [nx,ny,nz], sum_rgb i32 [3,nx,ny,nz] (planar, as
+ * colors above), count_rgb i32 [nx,ny,nz].  state = sum over frames of sign * obs(frame): integer addition commutes and
+ * has an exact inverse, so the state depends on neither the order of the frames nor on how they are cut into batches
+ * and calls, and adding a frame with sign -1 undoes, bit for bit, adding the same inputs with sign +1.
+ *
+ * gs_tsdf_accumulate: k frames, GS_TSDF_BATCH per launch.  Lattice, depth, mask, images, w2c and intrinsics exactly as
+ *   gs_tsdf_integrate takes them; sign i32 [k] (device), an integer multiplier (+1 adds, -1 removes).  sum_rgb and
+ *   count_rgb may both be NULL when images is NULL (they are then neither read nor written); images with either of them
+ *   NULL, a lattice size outside [2, 1024], a NULL state, depth, w2c or sign, h, w < 1, h * w > 2^30, k < 0 or fx, fy,
+ *   voxel, trunc <= 0 return GS_ERR_INVALID_ARG before anything is launched; k == 0 launches nothing.  Per lattice
+ *   point and frame, gs_tsdf_integrate's sequence operation for operation up to and including
+ *
+ *     s = fminf(1.0f, sdf / trunc)                        (reached only with sdf >= -trunc, so -1 <= s <= 1)
+ *
+ *   and then, in i32:
+ *
+ *     q = (int)rintf(s * 16384.0f)                        (|q| <= 16384; the product by 2^14 is exact, rintf rounds
+ *                                                          to nearest, ties to even: the one rounding of the value)
+ *     sum_s += sign * q ; count += sign
+ *     if images and sdf <= trunc, per channel:
+ *       c = (int)rintf(fminf(fmaxf(img, 0.0f), 1.0f) * 255.0f)      (a NaN image value gives 0: fmaxf returns the 0)
+ *       sum_rgb += sign * c
+ *     and once: count_rgb += sign
+ *
+ *   There is no weight cap (a cap is not linear).  With at most 65535 frames alive |sum_s| <= 16384 * 65535 < 2^30.
+ * gs_tsdf_resolve: the state as gs_tsdf_integrate's lattices; every element of the outputs is written.
+ *     weight = (float)max(count, 0)
+ *     tsdf   = count > 0 ? (float)((double)sum_s / ((double)count * 16384.0)) : 1.0f
+ *     colors = count_rgb > 0 ? (float)((double)sum_rgb / ((double)count_rgb * 255.0)) : 0.0f      (per channel)
+ *   The double product and quotient round once each, then once to float.  colors, sum_rgb and count_rgb are all NULL or
+ *   all given.  A point no frame is alive at resolves to the bits a fresh volume holds (tsdf 1, weight 0, colours 0).
+ * gs_tsdf_frame_change: what moved between a fused observation and the buffers as they are now.  old_depth, cur_depth
+ *   f32 [k,h,w], w2c_old, w2c_new f32 [k,3,4], out f64 [k,4]; k == 0 launches nothing.  Per frame:
+ *     out[0] = the number of pixels with old > 0 && cur > 0
+ *     out[1] = the sum over those pixels of (double)fabsf(cur - old)
+ *     out[2] = |c_new - c_old|, c = -R^T t the camera centre
+ *     out[3] = |p_new - p_old|, p = R^T ((double)ref_depth * e_z - t) the point at ref_depth on the optical axis
+ *   c and p in fp64 from the fp32 matrix, per component j with column j of R: c_j = -((r0j*t0 + r1j*t1) + r2j*t2),
+ *   p_j = (r0j*(-t0) + r1j*(-t1)) + r2j*(ref - t2); |a - b| = sqrt((dx*dx + dy*dy) + dz*dz).  Equal matrices give exactly
+ *   0.  The sums run in a fixed order: thread t of 256 adds pixels t, t + 256, ... in increasing order, a wave adds its
+ *   64 partials by v += v[lane ^ m] for m = 32, 16, 8, 4, 2, 1, and the four waves' totals are added as
+ *   ((w0 + w1) + w2) + w3.  No atomics: two runs agree bitwise.                                                        */
+int gs_tsdf_accumulate(int* sum_s, int* count, int* sum_rgb, int* count_rgb, int nx, int ny, int nz, const float* depth,
+                       const float* mask, const float* images, const float* w2c, const int* sign, int k, int h, int w,
+                       float fx, float fy, float cx, float cy, float lo_x, float lo_y, float lo_z, float voxel,
+                       float trunc, gs_stream_t stream);
+int gs_tsdf_resolve(const int* sum_s, const int* count, const int* sum_rgb, const int* count_rgb, int nx, int ny, int nz,
+                    float* tsdf, float* weight, float* colors, gs_stream_t stream);
+int gs_tsdf_frame_change(const float* old_depth, const float* cur_depth, const float* w2c_old, const float* w2c_new, int k,
+                         int h, int w, float ref_depth, double* out, gs_stream_t stream);
+
 /* ---- raycast of that TSDF lattice: depth, normal and colour images (no counterpart in the reference),
  *      csrc/tsdf_raycast.hip; tests/tsdf_raycast_restatement.py restates it serially ----
  *
