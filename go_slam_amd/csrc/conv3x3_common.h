@@ -21,6 +21,12 @@ __device__ __forceinline__ void frag_lane(int r, int& grp, int& pos) {
   pos = r - 4 * ((q + 1) >> 1);
 }
 
+// inverse of frag_lane: the column r whose lane sits at rank `pos` of group `grp`
+__device__ __forceinline__ int frag_lane_inv(int grp, int pos) {
+  const int pq = pos >> 2;
+  return 4 * (2 * pq + (grp ^ ((0x6 >> pq) & 1))) + (pos & 3);
+}
+
 // pixel (row ty, column tx inside the workgroup's tile) of MFMA column r of pixel fragment i of wave-half wm
 template <int TW, bool LP>
 __device__ __forceinline__ void tile_pixel(int wm, int i, int r, int& ty, int& tx) {

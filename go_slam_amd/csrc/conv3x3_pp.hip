@@ -8,9 +8,10 @@
 // workgroup of the CU only overlaps with it by chance.  Here the overlap is built in:
 //
 //  * 512 threads = 8 waves = two groups of four; waves w and w + 4 share a SIMD.  Every wave alternates a READ phase
-//    (12 ds_read_b128: its A/B fragments of one tap) and a MATH phase (16 v_mfma_f32_32x32x16_f16), separated by
-//    workgroup barriers; group 1 runs one phase behind group 0 (one extra barrier up front), so on every SIMD one wave
-//    is on the matrix pipe while its partner is on the LDS pipe.  One instruction stream, no role branches.
+//    (12 ds_read_b128: its A/B fragments of one tap) and a MATH phase (32 v_mfma_f32_16x16x32_f16, each over the
+//    chunk's whole K = 32), separated by workgroup barriers; group 1 runs one phase behind group 0 (one extra barrier
+//    up front), so on every SIMD one wave is on the matrix pipe while its partner is on the LDS pipe.  One instruction
+//    stream, no role branches.
 //  * the workgroup owns 512 pixels (row-stacked tiling: the n images are one image of n*H rows, tiles of 512 / TW rows x
 //    TW columns run across image boundaries; vertical taps that would cross an image boundary read a zero slot) x 128
 //    output channels; K = 9 taps x C in chunks of 32 channels; the (TH+2) x (TW+2) input patch of a chunk is staged ONCE
@@ -22,28 +23,43 @@
 //    s_barrier, counted s_waitcnt vmcnt(N), never 0 in the loop); a buffer is read only in the phase AFTER the
 //    barrier that follows the wait which retires it (both groups' pieces).
 //  * patch layout [pixel][5 x 16-byte slots]: four channel groups + one pad slot, i.e. an 80-BYTE pixel stride.  The four
-//    DMA lanes of a pixel still read its 64 contiguous bytes (the fifth lane reads the zero page), and 16 consecutive
-//    pixels start 20 banks apart = 16 distinct multiples of 4 banks modulo 64: with the lane-permuted fragment mapping (a
-//    ds_read_b128 service group = 16 consecutive pixels of one patch row, conv3x3_common.h) every B-fragment read is
-//    bank-conflict-free WITHOUT an address swizzle, so a tap's shift and the second k-step are immediate offsets of the
-//    ds_read: the READ phase is 9 VALU + 12 LDS instructions (the XOR-swizzled 64-byte layout of rounds 2-3 needed 46
-//    VALU per tap for the same reads; bench keyframe 12.66 -> 12.48 ms).  Taps that would cross an image boundary read
-//    a zero region behind the DMA rounds (written once per workgroup) through a per-lane base selected up front.  Weight
-//    planes [8-channel group][128 channels][8] are conflict-free as they are.
+//    DMA lanes of a pixel still read its 64 contiguous bytes (the fifth lane reads the zero page).  Slot index = 5 x
+//    pixel + channel group, and a ds_read_b128 service group is conflict-free when its 16 lanes hit 16 distinct slots
+//    modulo 16.  Lane l of a 16x16x32 fragment holds MFMA column l & 15 and channel group l >> 4, so a service group
+//    ({0-3, 12-15, 20-27} and its three siblings) is 8 columns of channel group g and the 8 OTHER columns of group g + 1.
+//    One more channel group = 13 more pixels modulo 16 (5 x 13 = 1), and both halves of the service group have to
+//    satisfy this at once: that happens exactly when each half takes 8 pixels whose indices are all even (or all odd) and
+//    distinct modulo 16.  The column <-> pixel assignment of an MFMA is free, so sub-fragment s of a 32-pixel fragment
+//    is its pixels of column parity s: at TW = 16 the even (odd) columns of its two rows (patch rows are 18 pixels
+//    apart, even), at TW = 8 those of its four rows (rows 4 apart: 40 pixels = 8 modulo 16).  (Columns 16 s ... 16 s + 15
+//    of the former 32-wide fragment -- 8 consecutive pixels of two rows -- would be a 2-way conflict on every B read.)
+//    Every B-fragment read is bank-conflict-free WITHOUT an address swizzle, and a tap's shift and the second
+//    sub-fragment (the pixel to the right) are immediate offsets of the ds_read: the READ phase is 9 VALU + 12 LDS
+//    instructions (the XOR-swizzled 64-byte layout of rounds 2-3 needed 46 VALU per tap for the same reads; bench
+//    keyframe 12.66 -> 12.48 ms).  Taps that would cross an image boundary read a zero region behind the DMA rounds
+//    (written once per workgroup) through a per-lane base selected up front.  Weight planes [8-channel group][128
+//    channels][8] are conflict-free as they are: 16 consecutive channels per A fragment, 8 + 8 of two planes per group.
+//  * the accumulators are 32 (16) blocks of 16 channels x 16 pixels (4 registers each, 128 (64) in all).  The epilogue
+//    scatters them into the wave's LDS tile [32 pixels][64 (32) channels] with the pixels numbered as tile_pixel numbers
+//    a 32-pixel fragment (frag_lane_inv), so everything behind the tile -- the stores, the gate arithmetic, the EPI 4 tap
+//    products on 32x32x16 MFMAs -- sees the same tile as with any other main-loop shape.
 //  * LDS: 2 x 51.3 KB patch (6 DMA rounds + zero region) + 4 x 8 KB weights = 134.5 KB (TW = 16; 148 KB at TW = 8); one
 //    workgroup per CU, 2 waves per SIMD.
-//  * BN = 64 instantiation (flow_encoder[2], 128 -> 64 channels): the same schedule with ONE 32-channel fragment per wave
-//    (a wave owns 128 pixels x 32 channels: 8 MFMAs per phase against 10 fragment reads, so it is bound by the READ
-//    phase, not the matrix pipe); a tap's weight image is 4 KB = one piece per thread of waves 0-3, waves 4-7 issue a
+//  * BN = 64 instantiation (flow_encoder[2], 128 -> 64 channels): the same schedule with TWO 16-channel A fragments per
+//    wave (a wave owns 128 pixels x 32 channels: 16 MFMAs per phase against 10 fragment reads, so it is bound by the
+//    READ phase, not the matrix pipe); a tap's weight image is 4 KB = one piece per thread of waves 0-3, waves 4-7 issue a
 //    dummy 16-byte DMA from the zero page so that every wave's vmcnt arithmetic stays the same.
 #include "common.h"
 #include "conv3x3_common.h"
 
 namespace {
 
+typedef float float4v __attribute__((ext_vector_type(4)));
+
 constexpr int PP_KG = 4;            // 8-channel groups per 32-channel chunk
 constexpr int PP_PSTR = 5;          // 16-byte slots per patch pixel (80-byte pixel stride, see the header)
-// zero slots behind a patch buffer's DMA rounds: the largest tap offset (2 rows + 2 pixels) + the second k-step's + 2
+// zero slots behind a patch buffer's DMA rounds: the largest tap offset (2 rows + 2 pixels) + the second sub-fragment's
+// pixel fit into the round-up to 16 (static_assert in the kernel)
 constexpr int pp_zpad(int tw) { return (((2 * (tw + 2) + 2) * PP_PSTR + 3 + 15) / 16) * 16; }
 constexpr int pp_patch_slots(int tw) {
   return (((512 / tw + 2) * (tw + 2) * PP_PSTR + 511) / 512) * 512 + pp_zpad(tw);
@@ -125,7 +141,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(const _Float16* __re
   static_assert(BN == 128 || (BN == 64 && (EPI == 0 || EPI == 3)), "64-channel workgroups: plain / bias + ReLU only");
   constexpr int PP_BN = BN;                               // output channels per workgroup
   constexpr int PP_WTAP = PP_KG * PP_BN;                  // 16-byte slots of one tap's weight image (512 or 256)
-  constexpr int NJ = BN / 64;                             // 32-channel fragments per wave
+  constexpr int NJ = BN / 64;                             // 32-channel groups per wave
+  constexpr int NA = 2 * NJ;                              // 16-channel A fragments per wave
   constexpr int PP_TS = NJ == 2 ? 72 : 40;                // epilogue tile row stride in halves (16-byte aligned rows)
   constexpr int TH_ = 512 / TW, PW_ = TW + 2, NPX = (TH_ + 2) * PW_;
   constexpr int PSTR = PP_PSTR;                           // 16-byte slots per patch pixel: 4 channel groups + 1 pad
@@ -144,7 +161,16 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(const _Float16* __re
   const int grp2 = wv >> 2;                               // 0: leading group, 1: one phase behind
   const int wm = (wv & 1) + 2 * grp2;                     // pixel quarter of the 512-pixel tile
   const int wn = (wv >> 1) & 1;                           // channel half (64 of 128, or 32 of 64)
-  const int r = lane & 31, kgl = lane >> 5;
+  const int r = lane & 31, kgl = lane >> 5;              // epilogue tile row / half-wave (32-wide view of the wave)
+  const int m16 = lane & 15, kq = lane >> 4;              // MFMA row / column index, 8-channel group of the chunk
+  // Columns {0-3, 12-15} and {4-11} of a 16-lane quarter sit in different ds_read_b128 service groups; each takes 8 of
+  // the 16 pixels of a sub-fragment: `sgh` = which 8, `idx8` = rank among them (see the header: fragment mapping).
+  const int sgh = ((m16 + 4) >> 3) & 1;
+  const int idx8 = sgh ? m16 - 4 : (m16 & 3) + 4 * (m16 >> 3);
+  // rank inside its 16-pixel row group (frag_lane's `pos`) of this lane's pixel in sub-fragment 0; sub-fragment 1 is
+  // the pixel to its right.  rr[s] = the column of the 32-wide view that tile_pixel maps to that pixel.
+  const int pos0 = TW == 16 ? 2 * idx8 : 8 * (idx8 >> 2) + 2 * (idx8 & 3);
+  const int rr[2] = {frag_lane_inv(sgh, pos0), frag_lane_inv(sgh, pos0 + 1)};
   int tix, nb;
   decode_block(blockIdx.x, gridDim.x / NB, NB, xcd, tix, nb);
   const int tx0 = (tix % tiles_x) * TW;
@@ -153,13 +179,14 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(const _Float16* __re
   const int T = nchunk * 9;                               // taps in all
   const half8* wsrc = wpack + (size_t)nb * T * PP_WTAP;
 
-  // this lane's pixel in the 4 pixel fragments of its wave, and whether it sits on the first / last row of its image
+  // this lane's pixel in sub-fragment 0 of the 4 pixel fragments of its wave (sub-fragment 1: one pixel to the right,
+  // same row), and whether it sits on the first / last row of its image
   int pb[4];
   bool top[4], bot[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     int ty, tx;
-    tile_pixel<TW, true>(wm, i, r, ty, tx);
+    tile_pixel<TW, true>(wm, i, rr[0], ty, tx);
     pb[i] = ty * PW_ + tx;
     const int yy = (g0 + ty) % H;
     top[i] = yy == 0;
@@ -179,13 +206,14 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(const _Float16* __re
     poff[q] = off;
   }
 
-  // slot (pixel * 5 + channel group of this half-wave) of this lane's pixel in each fragment: the tap shift and the
-  // second k-step are immediate offsets of the ds_read.  Lanes whose row above (below) belongs to another image read the
-  // zero region instead for the taps of the upper (lower) kernel row.
+  // slot (pixel * 5 + channel group of this lane's quarter) of this lane's pixel in each fragment: the tap shift and the
+  // second sub-fragment are immediate offsets of the ds_read.  Lanes whose row above (below) belongs to another image
+  // read the zero region instead for the taps of the upper (lower) kernel row.
+  static_assert((2 * PW_ + 2) * PSTR + PSTR < ZPAD, "masked taps of the second sub-fragment stay inside the zero region");
   int vb[4], vt[4], vo[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    vb[i] = pb[i] * PSTR + kgl;
+    vb[i] = pb[i] * PSTR + kq;
     vt[i] = top[i] ? ZSLOT : vb[i];
     vo[i] = bot[i] ? ZSLOT : vb[i];
   }
@@ -196,25 +224,36 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(const _Float16* __re
     static_assert(2 * ZPAD <= 512, "one store per thread");
   }
 
-  float16v acc[NJ][4];
+  // acc[jj][i][s]: 16 channels (16 jj ... + 15 of the wave's) x the 16 pixels of sub-fragment s of fragment i; a lane
+  // holds channels 4 kq ... + 3 of pixel column m16
+  float4v acc[NA][4][2];
 #pragma unroll
-  for (int j = 0; j < NJ; ++j)
+  for (int jj = 0; jj < NA; ++jj)
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int e = 0; e < 16; ++e) acc[j][i][e] = 0.0f;
-  half8 a[2][NJ], b[2][4];
+      for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[jj][i][s][e] = 0.0f;
+  half8 a[NA], b[4][2];
 
   // ---- the three building blocks --------------------------------------------------------------------------------
   auto issue_patch = [&](int src_chunk, int buf, int q, int off) {        // one 512-slot round of a patch
     const void* src = (const void*)pp_zero_page;
-    if (off >= 0) {
+    if constexpr (EPI == 1 || EPI == 2) {
+      // Two input tensors: [x (first `split` channels) | xb].  `split` is a multiple of 32, so a chunk lies in one of
+      // them: a scalar choice.  The address is formed for every lane (pixel 0 where the slot is a zero slot) and then
+      // selected, so that no branch splits the MATH phase this runs in.
+      const int o = off < 0 ? 0 : off;
+      const bool first = src_chunk * 32 < ep.split;
+      const _Float16* bp = first ? x : ep.xb;
+      const int st = first ? xs : ep.xsb;
+      const _Float16* p = bp + (size_t)(o >> 2) * st + (src_chunk * 32 - (first ? 0 : ep.split) + (o & 3) * 8);
+      if (off >= 0) src = (const void*)p;
+    } else if (off >= 0) {
       const size_t pix = (size_t)(off >> 2);
       const int c0 = src_chunk * 32 + (off & 3) * 8;
-      if constexpr (EPI == 1 || EPI == 2)                  // two input tensors: [x (first `split` channels) | xb]
-        src = c0 < ep.split ? (const void*)(x + pix * xs + c0) : (const void*)(ep.xb + pix * ep.xsb + (c0 - ep.split));
-      else
-        src = (const void*)(x + pix * xs + c0);
+      src = (const void*)(x + pix * xs + c0);
     }
     pp_glds16(src, pbuf + buf * PSLOTS + q * 512 + wv * 64);
   };
@@ -231,11 +270,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(const _Float16* __re
     const half8* pp = pbuf + pbuf_ix * PSLOTS;
     const int dy = tap / 3, toff = dy * PW_ + (tap % 3);
 #pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const int kg = 2 * s + kgl;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) a[s][j] = wb[kg * PP_BN + wn * (PP_BN / 2) + 32 * j + r];
-    }
+    for (int jj = 0; jj < NA; ++jj) a[jj] = wb[kq * PP_BN + wn * (PP_BN / 2) + 16 * jj + m16];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       int base = dy == 0 ? vt[i] : dy == 2 ? vo[i] : vb[i];     // the row above / below belongs to another image: zeros
@@ -244,34 +279,30 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(const _Float16* __re
       }
       asm volatile("" : "+v"(base));                      // opaque: one address register per read pair, not 24 hoisted ones
       const half8* q = pp + base;
-      b[0][i] = q[toff * PSTR];                           // channel group kgl (first k-step) ...
-      b[1][i] = q[toff * PSTR + 2];                       // ... and 2 + kgl (second): immediate offsets
+      b[i][0] = q[toff * PSTR];                           // sub-fragment 0 ...
+      b[i][1] = q[toff * PSTR + PSTR];                    // ... and 1, the pixel to the right: immediate offsets
     }
   };
-  // MATH phase body: 16 MFMAs; `between` (the LDS-DMA issue of this tap) is placed after the first four, so that its
-  // address arithmetic issues in the shadow of running MFMAs instead of delaying the first one after the barrier
+  // MATH phase body: 32 (16) MFMAs, each over the chunk's whole K = 32; `between` (the LDS-DMA issue of this tap) is
+  // placed after the first quarter, so that its address arithmetic issues in the shadow of running MFMAs instead of
+  // delaying the first one after the barrier
   bool prio = true;
   if constexpr (PROBE) prio = !(ep.variant & 1);
+  auto mfma_frag = [&](int i) {
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int jj = 0; jj < NA; ++jj)
+        acc[jj][i][s] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[jj], b[i][s], acc[jj][i][s], 0, 0, 0);
+  };
   auto math = [&](auto&& between) {
     if (prio) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-        acc[j][i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0][j], b[0][i], acc[j][i], 0, 0, 0);
+    mfma_frag(0);
     __builtin_amdgcn_sched_barrier(0);
     between();
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int i = 2; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-        acc[j][i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0][j], b[0][i], acc[j][i], 0, 0, 0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-        acc[j][i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1][j], b[1][i], acc[j][i], 0, 0, 0);
+    for (int i = 1; i < 4; ++i) mfma_frag(i);
     if (prio) __builtin_amdgcn_s_setprio(0);
   };
 
@@ -337,7 +368,6 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(const _Float16* __re
       // head's product.  wn = 0 starts from zero and hands its 16 accumulator registers over through LDS; wn = 1 goes
       // on from them -- one accumulation chain in conv3x3_head_kernel's order.  The hand-over slots (4 KB per pair,
       // two per pair: wn = 0 fills fragment i + 1's while wn = 1 drains fragment i's) lie behind the eight tiles.
-      typedef float float4v __attribute__((ext_vector_type(4)));
       typedef float float2v __attribute__((ext_vector_type(2)));
       float4v* const hand = reinterpret_cast<float4v*>(reinterpret_cast<_Float16*>(smem) + 8 * 32 * PP_TS);
       static_assert((8 * 32 * PP_TS * 2) % 16 == 0 && 8 * 32 * PP_TS * 2 + 2 * 4 * 4096 <= 2 * PSLOTS * 16, "hand-over");
@@ -354,13 +384,13 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(const _Float16* __re
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
 #pragma unroll
-        for (int j = 0; j < NJ; ++j)
+        for (int jj = 0; jj < NA; ++jj)
 #pragma unroll
-          for (int g = 0; g < 4; ++g) {
+          for (int s = 0; s < 2; ++s) {                   // C layout: row (channel) = 4 kq + e, col (pixel) = m16
             half4 o;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = (_Float16)acc[j][i][4 * g + e];
-            *reinterpret_cast<half4*>(tile + r * PP_TS + j * 32 + 8 * g + 4 * kgl) = o;
+            for (int e = 0; e < 4; ++e) o[e] = (_Float16)acc[jj][i][s][e];
+            *reinterpret_cast<half4*>(tile + rr[s] * PP_TS + 16 * jj + 4 * kq) = o;
           }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -453,14 +483,15 @@ __global__ __launch_bounds__(512, 1) void conv3x3_pp_kernel(const _Float16* __re
       }
     }
     // (2) accumulators -> [32 pixels][64 (32) channels] fp16 tile
+    //     (row rr[s] = the pixel of column m16 of sub-fragment s, as tile_pixel numbers the fragment's 32 pixels)
 #pragma unroll
-    for (int j = 0; j < NJ; ++j)
+    for (int jj = 0; jj < NA; ++jj)
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {                       // C layout: row (channel) = 8 g + 4 (lane >> 5) + e, col = pixel
+      for (int s = 0; s < 2; ++s) {                       // C layout: row (channel) = 4 (lane >> 4) + e, col = pixel
         half4 o;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = (_Float16)acc[j][i][4 * g + e];
-        *reinterpret_cast<half4*>(tile + r * PP_TS + j * 32 + 8 * g + 4 * kgl) = o;
+        for (int e = 0; e < 4; ++e) o[e] = (_Float16)acc[jj][i][s][e];
+        *reinterpret_cast<half4*>(tile + rr[s] * PP_TS + 16 * jj + 4 * kq) = o;
       }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
