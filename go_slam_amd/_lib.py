@@ -66,6 +66,11 @@ SIGNATURES = {
     "gs_esdf_build": (c_int, [_P, _P, c_int, c_int, c_int, c_float, c_int, c_float, _P, _P, _P, _P]),
     "gs_esdf_query": (c_int, [_P, _P] + [c_int] * 3 + [c_float] * 4 + [_P, c_int, _P, _P, _P, _P]),
     "gs_esdf_slice": (c_int, [_P] * 3 + [c_int] * 8 + [_P, _P, _P]),
+    "gs_geodesic_brick": (c_int, [ctypes.POINTER(c_int)] * 3),
+    "gs_geodesic_flags_bytes": (c_size_t, [c_int] * 3),
+    "gs_geodesic_init": (c_int, [_P] + [c_int] * 3 + [_P, c_int, _P, _P, _P]),
+    "gs_geodesic_relax": (c_int, [_P] + [c_int] * 4 + [_P, _P, c_int, c_int, _P, _P]),
+    "gs_geodesic_path": (c_int, [_P, _P] + [c_int] * 7 + [_P, _P, _P]),
     "gs_frame_prep_color": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P]),
     "gs_frame_prep_depth": (c_int, [_P, c_int, c_float, c_int, c_int, c_int, c_int, _P]),
     "gs_cvx_upsample":(c_int, [_P] * 4 + [c_int] * 4 + [_P]),

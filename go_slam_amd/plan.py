@@ -1,0 +1,258 @@
+"""Collision-free paths over a passability lattice: the cost-to-go field and the path walked down it (csrc/geodesic.hip).
+
+`geodesic_field` relaxes, brick by brick on the GPU, the length of the shortest route from every passable cell to a set
+of seed cells -- 26 moves of 1000 / 1414 / 1732 milli-voxels that cut no corner -- and `GeodesicField.path` walks from a
+cell down to a seed.  The field is integer and the unique fixed point of its relaxation, so it equals a serial Dijkstra
+bit for bit (tests/geodesic_restatement.py; include/goslam_hip.h, gs_geodesic_*).
+`ESDF.passable` / `plan` / `reachable` (tsdf.py) put a fused volume's distance field under it, `plan_on_map` a 2-D
+occupancy map, and `path_text` / `parse_path` are the run's map/path.txt.
+"""
+import ctypes
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+
+INF = 0x3fffffff                       # GS_GEO_INF
+MAX_COST = INF - 1732                  # GS_GEO_MAX_COST
+MAX_CELLS = 1024                       # per axis
+SWEEP_BATCH = 8                        # sweeps enqueued per host read of `changed`
+MAP_FREE, MAP_UNKNOWN = 254, 205       # tsdf.MAP_FREE, tsdf.MAP_UNKNOWN
+
+
+def _cell(cell, dims, what):
+    try:
+        c = [int(v) for v in (cell.tolist() if hasattr(cell, "tolist") else cell)]
+    except (TypeError, ValueError):
+        c = None
+    if c is None or len(c) != 3:
+        raise ValueError(f"{what}: a cell is three integers (got {cell!r})")
+    if not all(0 <= c[i] < dims[i] for i in range(3)):
+        raise ValueError(f"{what}: cell {tuple(c)} lies outside the lattice {tuple(dims)}")
+    return c
+
+
+class GeodesicField:
+    """A cost-to-go field at its fixed point: `.cost` int32 [n0,n1,n2] in milli-voxels (INF = 0x3fffffff where no seed
+    is reachable within the cap), `.passable` uint8 [n0,n1,n2] it was built over, `.dims`, and `.sweeps`, the number of
+    brick sweeps that were needed (the last of them lowered nothing; it may differ between runs, the field does not)."""
+
+    def __init__(self, cost, passable, sweeps):
+        self.cost, self.passable, self.sweeps = cost, passable, int(sweeps)
+        self.dims = tuple(int(n) for n in cost.shape)
+        self.device = cost.device
+
+    @torch.no_grad()
+    def path(self, start_cell, max_len=None):
+        """The cells int32 [L,3] (on the device) from `start_cell` down to a seed, both included (gs_geodesic_path): each
+        step takes the allowed neighbour with the smallest cost + weight, ties to the lowest move index.  L = 0 when
+        the start holds INF.  `max_len` defaults to min(number of cells, cost[start] / 1000 + 2), which always suffices;
+        RuntimeError when a given max_len does not.  One 4-byte read of cost[start], one of the length."""
+        what = "GeodesicField.path"
+        c = _cell(start_cell, self.dims, what)
+        if max_len is not None and (isinstance(max_len, bool) or int(max_len) != max_len or int(max_len) < 1):
+            raise ValueError(f"{what}: max_len must be a positive integer (got {max_len!r})")
+        at_start = int(self.cost[c[0], c[1], c[2]].item())
+        if at_start >= INF:
+            return torch.zeros((0, 3), dtype=torch.int32, device=self.device)
+        if max_len is None:
+            max_len = min(self.cost.numel(), at_start // 1000 + 2)
+        max_len = int(max_len)
+        cells = torch.empty((max_len, 3), dtype=torch.int32, device=self.device)
+        n = torch.empty(1, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = _lib.lib().gs_geodesic_path(_lib.ptr(self.cost), _lib.ptr(self.passable), *self.dims, *c, max_len,
+                                             _lib.ptr(cells), _lib.ptr(n), _lib.stream_ptr(self.device))
+        _lib.check(rc, what)
+        n = int(n.item())
+        if n < 0:
+            raise RuntimeError(f"{what}: {max_len} cells do not reach a seed from {tuple(c)} (cost {at_start})")
+        return cells[:n]
+
+
+def field_arguments(passable, seeds, max_cost=None, max_sweeps=65536):
+    """(dims, seeds int32 [m,3] on the host, max_cost, max_sweeps) of `geodesic_field`, or ValueError.  Touches no
+    device."""
+    what = "geodesic_field"
+    if not isinstance(passable, torch.Tensor) or passable.dtype not in (torch.uint8, torch.bool):
+        raise ValueError(f"{what}: passable must be a uint8 or bool tensor "
+                         f"(got {getattr(passable, 'dtype', type(passable).__name__)})")
+    if passable.dim() != 3 or not all(1 <= int(n) <= MAX_CELLS for n in passable.shape):
+        raise ValueError(f"{what}: passable must be [n0,n1,n2] with every size in [1, {MAX_CELLS}] "
+                         f"(got {list(passable.shape)}); a 2-D map [n_u,n_v] is the lattice [1,n_u,n_v]")
+    dims = tuple(int(n) for n in passable.shape)
+    s = seeds.detach().cpu().numpy() if isinstance(seeds, torch.Tensor) else np.asarray(seeds)
+    if s.size == 0:
+        s = np.zeros((0, 3), dtype=np.int32)
+    if s.ndim != 2 or s.shape[1] != 3 or not (np.issubdtype(s.dtype, np.integer) and s.dtype != np.bool_):
+        raise ValueError(f"{what}: seeds must be integers [m,3] (got {s.dtype} {list(s.shape)})")
+    if ((s < 0) | (s >= np.asarray(dims)[None, :])).any():
+        raise ValueError(f"{what}: a seed lies outside the lattice {dims}")
+    if max_cost is None:
+        max_cost = MAX_COST
+    if isinstance(max_cost, bool) or not isinstance(max_cost, (int, np.integer)) or not 0 <= int(max_cost) <= MAX_COST:
+        raise ValueError(f"{what}: max_cost must be an integer in [0, {MAX_COST}] milli-voxels (got {max_cost!r})")
+    if isinstance(max_sweeps, bool) or not isinstance(max_sweeps, (int, np.integer)) or int(max_sweeps) < 1:
+        raise ValueError(f"{what}: max_sweeps must be a positive integer (got {max_sweeps!r})")
+    return dims, np.ascontiguousarray(s, dtype=np.int32), int(max_cost), int(max_sweeps)
+
+
+def brick():
+    """The relaxation's brick (b0, b1, b2) in cells (gs_geodesic_brick)."""
+    b = [ctypes.c_int(0) for _ in range(3)]
+    _lib.check(_lib.lib().gs_geodesic_brick(*[ctypes.byref(v) for v in b]), "gs_geodesic_brick")
+    return tuple(v.value for v in b)
+
+
+@torch.no_grad()
+def geodesic_field(passable, seeds, max_cost=None, max_sweeps=65536):
+    """The cost-to-go field over `passable` (uint8 or bool [n0,n1,n2], non-zero where the robot's centre may be; on the
+    GPU, or moved there) from the cells `seeds` (integers [m,3]; a blocked seed is ignored): a `GeodesicField`.  Costs
+    above `max_cost` (milli-voxels, default and at most 0x3fffffff - 1732) are INF.  Sweeps are enqueued in batches of
+    SWEEP_BATCH (gs_geodesic_relax) and `changed` is read once per batch until a sweep lowered nothing; RuntimeError
+    when `max_sweeps` sweeps do not get there.  ValueError for bad shapes, dtypes, seeds outside the lattice or a
+    max_cost out of range, before the device is touched."""
+    dims, seeds, max_cost, max_sweeps = field_arguments(passable, seeds, max_cost, max_sweeps)
+    L = _lib.lib()
+    dev = passable.device if passable.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    passable = passable.to(device=dev, dtype=torch.uint8).contiguous()
+    cost = torch.empty(dims, dtype=torch.int32, device=dev)
+    flags = torch.empty(L.gs_geodesic_flags_bytes(*dims), dtype=torch.uint8, device=dev)
+    changed = torch.empty(SWEEP_BATCH, dtype=torch.int32, device=dev)        # u32 0 / 1
+    seeds_d = torch.from_numpy(seeds).to(dev)
+    m = int(seeds.shape[0])
+    with torch.cuda.device(dev):
+        stream = _lib.stream_ptr(dev)
+        _lib.check(L.gs_geodesic_init(_lib.ptr(passable), *dims, _lib.ptr(seeds_d) if m else None, m, _lib.ptr(cost),
+                                      _lib.ptr(flags), stream), "geodesic_field (init)")
+        sweeps = 0
+        while True:
+            k = min(SWEEP_BATCH, max_sweeps - sweeps)
+            if k <= 0:
+                raise RuntimeError(f"geodesic_field: no fixed point after max_sweeps = {max_sweeps} sweeps")
+            _lib.check(L.gs_geodesic_relax(_lib.ptr(passable), *dims, max_cost, _lib.ptr(cost), _lib.ptr(flags), sweeps,
+                                           k, _lib.ptr(changed), stream), "geodesic_field (relax)")
+            quiet = (changed[:k] == 0).cpu().tolist()                         # the batch's one read
+            if True in quiet:
+                sweeps += quiet.index(True) + 1
+                break
+            sweeps += k
+    return GeodesicField(cost, passable, sweeps)
+
+
+def snap_cell(passable, cell, radius_cells):
+    """`cell` (three integers, possibly outside the lattice) if it is inside and passable, else the passable cell at the
+    smallest squared lattice distance <= radius_cells^2 from it, ties to the lowest linear index, else None.  torch on
+    the window of the lattice that the radius covers; one small read."""
+    dims = tuple(int(n) for n in passable.shape)
+    c = [int(v) for v in cell]
+    inside = all(0 <= c[i] < dims[i] for i in range(3))
+    if inside and int(passable[c[0], c[1], c[2]].item()) != 0:
+        return c
+    r = int(math.floor(radius_cells))
+    if r <= 0:
+        return None
+    lo = [max(c[i] - r, 0) for i in range(3)]
+    hi = [min(c[i] + r, dims[i] - 1) for i in range(3)]
+    if any(lo[i] > hi[i] for i in range(3)):
+        return None
+    dev = passable.device
+    ax = [torch.arange(lo[i], hi[i] + 1, dtype=torch.int64, device=dev) for i in range(3)]
+    g0, g1, g2 = torch.meshgrid(*ax, indexing="ij")
+    d2 = (g0 - c[0]) ** 2 + (g1 - c[1]) ** 2 + (g2 - c[2]) ** 2
+    lin = (g0 * dims[1] + g1) * dims[2] + g2
+    window = passable[lo[0]:hi[0] + 1, lo[1]:hi[1] + 1, lo[2]:hi[2] + 1] != 0
+    ok = window & (d2.double() <= float(radius_cells) ** 2)
+    key = torch.where(ok, d2 * (1 << 31) + lin, torch.full_like(d2, 1 << 62))    # d2 <= 3 * 1024^2, lin < 2^30
+    best = int(key.min().item())
+    if best >= 1 << 62:
+        return None
+    lin = best & ((1 << 31) - 1)
+    return [lin // (dims[1] * dims[2]), lin // dims[2] % dims[1], lin % dims[2]]
+
+
+@torch.no_grad()
+def plan_on_map(grid, start_xy, goal_xy, allow_unknown=False):
+    """Plan on the 2-D map `grid` (the dict of `ESDF.occupancy_slice` or `load_map`: cells uint8 [n_u,n_v], origin,
+    resolution) from `start_xy` to `goal_xy` (map coordinates along the two image axes).  A cell passes when it is free
+    (254), with `allow_unknown` also when unknown (205); the lattice is [1,n_u,n_v]; a point's cell is
+    floor((xy - origin) / resolution).  -> {"reachable", "cells": int32 [L,2] (u, v) start to goal on the device,
+    "points": float64 [L,2], their centres origin + (cell + 0.5) * resolution, "length_m", "start_cell", "goal_cell",
+    "sweeps"}; unreachable: L = 0 and length_m inf.  ValueError for a point outside the map, before the device is
+    touched."""
+    what = "plan_on_map"
+    cells = grid["cells"]
+    cells = cells if isinstance(cells, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(cells))
+    if cells.dim() != 2 or cells.dtype != torch.uint8:
+        raise ValueError(f"{what}: cells must be uint8 [n_u,n_v] (got {cells.dtype} {list(cells.shape)})")
+    res = float(grid["resolution"])
+    origin = [float(v) for v in grid["origin"]]
+    if not res > 0:
+        raise ValueError(f"{what}: resolution must be positive (got {res})")
+    ends = []
+    for name, xy in (("start_xy", start_xy), ("goal_xy", goal_xy)):
+        try:
+            x, y = (float(v) for v in xy)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: {name} must be (x, y) (got {xy!r})") from None
+        if not (math.isfinite(x) and math.isfinite(y)):
+            raise ValueError(f"{what}: {name} {xy!r} is not finite")
+        uv = (int(math.floor((x - origin[0]) / res)), int(math.floor((y - origin[1]) / res)))
+        if not (0 <= uv[0] < cells.shape[0] and 0 <= uv[1] < cells.shape[1]):
+            raise ValueError(f"{what}: {name} {xy!r} is cell {uv}, outside the map {list(cells.shape)}")
+        ends.append(uv)
+    passable = cells == MAP_FREE
+    if allow_unknown:
+        passable = passable | (cells == MAP_UNKNOWN)
+    field = geodesic_field(passable[None].contiguous(), [[0, ends[1][0], ends[1][1]]])
+    path = field.path([0, ends[0][0], ends[0][1]])[:, 1:].contiguous()
+    reachable = int(path.shape[0]) > 0
+    length = float(field.cost[0, ends[0][0], ends[0][1]].item()) * res / 1000.0 if reachable else math.inf
+    points = torch.tensor(origin, dtype=torch.float64, device=path.device)[None, :] + (path.double() + 0.5) * res
+    return {"reachable": reachable, "cells": path, "points": points, "length_m": length, "start_cell": ends[0],
+            "goal_cell": ends[1], "sweeps": field.sweeps}
+
+
+PATH_REPORT_ORDER = ("reachable", "length_m", "min_clearance_m", "n_points")
+
+
+def path_text(result):
+    """The text of map/path.txt for `ESDF.plan`'s dict: two header lines, `name<TAB>repr(value)` for reachable,
+    length_m, min_clearance_m and n_points, then one `x y z` line per point with repr(): reading the file gives back
+    the numbers bit for bit."""
+    pts = result["points"]
+    pts = pts.detach().cpu().numpy() if isinstance(pts, torch.Tensor) else np.asarray(pts)
+    pts = np.asarray(pts, dtype=np.float64).reshape(-1, 3)
+    head = {"reachable": bool(result["reachable"]), "length_m": float(result["length_m"]),
+            "min_clearance_m": float(result["min_clearance_m"]), "n_points": int(pts.shape[0])}
+    lines = ["Collision-free path through the fused TSDF volume's distance field, start to goal: the centres [m] of the "
+             "lattice cells of the shortest route that keeps the robot's radius from every surface",
+             "(length_m: its length; min_clearance_m: the smallest distance to a surface along it; inf and nan when the "
+             "goal cannot be reached; then per point: x y z)"]
+    lines += [f"{k}\t{head[k]!r}" for k in PATH_REPORT_ORDER]
+    lines += [f"{float(p[0])!r} {float(p[1])!r} {float(p[2])!r}" for p in pts]
+    return "\n".join(lines) + "\n"
+
+
+def parse_path(text):
+    """path_text's inverse: ({"reachable", "length_m", "min_clearance_m", "n_points"}, points float64 [n,3])."""
+    lines = text.splitlines()
+    if len(lines) < 2 + len(PATH_REPORT_ORDER) or not lines[0].startswith("Collision-free path through"):
+        raise ValueError("not a map/path.txt")
+    result = {}
+    for key, line in zip(PATH_REPORT_ORDER, lines[2:]):
+        name, value = line.split("\t")
+        if name != key:
+            raise ValueError(f"path.txt: expected {key}, found {name}")
+        if key == "reachable":
+            if value not in ("True", "False"):
+                raise ValueError(f"path.txt: reachable is {value!r}")
+            result[key] = value == "True"
+        else:
+            result[key] = int(value) if key == "n_points" else float(value)
+    rows = [[float(v) for v in line.split(" ")] for line in lines[2 + len(PATH_REPORT_ORDER):]]
+    if len(rows) != result["n_points"] or any(len(r) != 3 for r in rows):
+        raise ValueError("path.txt: the points do not match n_points")
+    return result, np.array(rows, dtype=np.float64).reshape(-1, 3)

@@ -17,6 +17,10 @@ gradient at world points, `ESDF.occupancy_slice` / `save_map` flatten a slab int
 `trajectory_clearance` reports how close the estimated camera centres come to the fused surfaces
 (metrics_tsdf_clearance.txt).  tests/esdf_restatement.py restates the field.
 
+csrc/geodesic.hip answers where to go: `ESDF.passable` marks the lattice points a robot of a given radius may occupy,
+`ESDF.plan` finds the shortest collision-free route between two world points and `ESDF.reachable` what can be reached
+at all (plan.py: the cost-to-go field and the walk down it; tests/geodesic_restatement.py).
+
 tsdf_live.py keeps such a volume during a run, while the poses still move; it fuses through
 `keyframe_observations`, the rule `fuse_keyframes` applies per chunk.
 """
@@ -27,6 +31,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import plan as _plan
 from .lietorch_shim import SE3
 from .neus.mesh import Mesh, marching_cubes
 from .pointcloud import _host_index, _rows, ply_colors
@@ -372,6 +377,106 @@ class ESDF:
         return {"cells": cells, "clearance": clearance, "resolution": self.voxel, "axes": (u, v),
                 "origin": (float(self.lo[u] - 0.5 * self.voxel), float(self.lo[v] - 0.5 * self.voxel))}
 
+    def _radius_d2(self, robot_radius, what):
+        """floor((robot_radius / voxel)^2), the squared lattice distance a passable cell must exceed; ValueError for a
+        radius outside the field's band (slice_arguments' rule)."""
+        robot_radius = float(robot_radius)
+        if not 0 <= robot_radius <= self.radius_voxels * self.voxel:
+            raise ValueError(f"{what}: robot_radius {robot_radius} m outside [0, {self.radius_voxels * self.voxel}], "
+                             "the band of this field (build it with a larger max_distance)")
+        return int(math.floor((robot_radius / self.voxel) ** 2))
+
+    @torch.no_grad()
+    def passable(self, robot_radius=0.0, allow_unknown=False):
+        """uint8 [nx,ny,nz]: 1 where the centre of a robot of `robot_radius` metres may be -- the point was seen free
+        (with `allow_unknown`: was not seen solid) and its squared distance to the nearest site exceeds
+        floor((robot_radius / voxel)^2): the complement of `occupancy_slice`'s occupied rule.  Elementwise torch, once
+        per plan.  ValueError for a radius beyond the field's band."""
+        occ_d2 = self._radius_d2(robot_radius, "ESDF.passable")
+        seen = (self.state != 2) if allow_unknown else (self.state == 1)
+        return (seen & (self.d2 > occ_d2)).to(torch.uint8)
+
+    def plan_arguments(self, points, robot_radius=0.0, snap=0.0, max_cost_m=None, what="ESDF.plan"):
+        """(nearest lattice cells of the world `points`, snap radius in cells, max_cost in milli-voxels or None) for
+        `plan` and `reachable`, or ValueError: a point that is no three finite numbers, a radius beyond the band, a
+        negative snap, a point whose cell lies outside the lattice while snap is 0, a max_cost_m that is not positive
+        or beyond 0x3fffffff - 1732 milli-voxels.  Touches no device."""
+        self._radius_d2(robot_radius, what)
+        snap = float(snap)
+        if not (snap >= 0 and math.isfinite(snap)):
+            raise ValueError(f"{what}: snap must be a finite distance >= 0 in metres (got {snap})")
+        max_cost = None
+        if max_cost_m is not None:
+            max_cost_m = float(max_cost_m)
+            if not (max_cost_m > 0 and max_cost_m / self.voxel * 1000.0 <= _plan.MAX_COST):
+                raise ValueError(f"{what}: max_cost_m must be positive and at most "
+                                 f"{_plan.MAX_COST * self.voxel / 1000.0} m on this lattice (got {max_cost_m})")
+            max_cost = int(math.floor(max_cost_m / self.voxel * 1000.0))
+        cells = []
+        for p in points:
+            try:
+                xyz = [float(v) for v in (p.tolist() if hasattr(p, "tolist") else p)]
+            except (TypeError, ValueError):
+                xyz = []
+            if len(xyz) != 3 or not all(math.isfinite(v) for v in xyz):
+                raise ValueError(f"{what}: a point is three finite world coordinates (got {p!r})")
+            cell = [int(math.floor((xyz[a] - self.lo[a]) / self.voxel + 0.5)) for a in range(3)]
+            if snap == 0 and not all(0 <= cell[a] < self.dims[a] for a in range(3)):
+                raise ValueError(f"{what}: point {xyz} is lattice point {cell}, outside the lattice {self.dims} "
+                                 "(snap > 0 moves an endpoint to the nearest passable cell)")
+            cells.append(cell)
+        return cells, snap / self.voxel, max_cost
+
+    @torch.no_grad()
+    def plan(self, start, goal, robot_radius=0.0, allow_unknown=False, snap=0.0, max_cost_m=None):
+        """The shortest collision-free route of a robot of `robot_radius` from the world point `start` to `goal` over
+        the lattice (plan.geodesic_field seeded at the goal, GeodesicField.path from the start).  A point maps to its
+        nearest lattice point; with `snap` > 0 metres an endpoint whose cell does not pass moves to the passable cell
+        at the smallest squared lattice distance within `snap`, ties to the lowest linear index (camera centres
+        usually sit in never-observed cells).  Routes longer than `max_cost_m` count as unreachable.  -> {"reachable",
+        "cells": int32 [L,3] on the device, "points": float64 [L,3] world coordinates start to goal, "length_m":
+        cost[start] * voxel / 1000, "min_clearance_m": the smallest `dist` over the path's cells, "start_cell",
+        "goal_cell" (None when no passable cell was found), "sweeps"}; unreachable: L = 0, length_m inf,
+        min_clearance_m nan.  ValueError (plan_arguments) before the device is touched."""
+        (s, g), snap_cells, max_cost = self.plan_arguments([start, goal], robot_radius, snap, max_cost_m)
+        passable = self.passable(robot_radius, allow_unknown)
+        s, g = _plan.snap_cell(passable, s, snap_cells), _plan.snap_cell(passable, g, snap_cells)
+        dev = self.device
+        out = {"reachable": False, "cells": torch.zeros((0, 3), dtype=torch.int32, device=dev),
+               "points": torch.zeros((0, 3), dtype=torch.float64, device=dev), "length_m": math.inf,
+               "min_clearance_m": math.nan, "start_cell": s, "goal_cell": g, "sweeps": 0}
+        if s is None or g is None:
+            return out
+        field = _plan.geodesic_field(passable, [g], max_cost)
+        cells = field.path(s)
+        out["sweeps"] = field.sweeps
+        if int(cells.shape[0]) == 0:
+            return out
+        idx = cells.long()
+        lo = torch.tensor(self.lo, dtype=torch.float64, device=dev)
+        scalars = torch.stack([field.cost[s[0], s[1], s[2]].double(),
+                               self.dist[idx[:, 0], idx[:, 1], idx[:, 2]].min().double()]).cpu().tolist()     # one read
+        out.update(reachable=True, cells=cells, points=lo[None, :] + cells.double() * self.voxel,
+                   length_m=scalars[0] * self.voxel / 1000.0, min_clearance_m=scalars[1])
+        return out
+
+    @torch.no_grad()
+    def reachable(self, seeds_world, robot_radius=0.0, allow_unknown=False, snap=0.0, max_cost_m=None):
+        """bool [nx,ny,nz]: the cells a robot of `robot_radius` can reach from any of the world points `seeds_world`
+        ([m,3], for example every camera centre), i.e. cost < INF of the field seeded at all of them.  Seeds are placed
+        as `plan` places its endpoints; one without a passable cell is ignored."""
+        seeds_world = seeds_world.detach().cpu().numpy() if isinstance(seeds_world, torch.Tensor) else seeds_world
+        pts = np.asarray(seeds_world, dtype=np.float64)
+        if pts.size == 0:
+            pts = pts.reshape(0, 3)
+        if pts.ndim != 2 or pts.shape[1] != 3:
+            raise ValueError(f"ESDF.reachable: seeds_world must be [m,3] (got {list(pts.shape)})")
+        cells, snap_cells, max_cost = self.plan_arguments(list(pts), robot_radius, snap, max_cost_m, "ESDF.reachable")
+        passable = self.passable(robot_radius, allow_unknown)
+        seeds = [c for c in (_plan.snap_cell(passable, c, snap_cells) for c in cells) if c is not None]
+        field = _plan.geodesic_field(passable, np.array(seeds, dtype=np.int32).reshape(-1, 3), max_cost)
+        return field.cost < _plan.INF
+
     def save_map(self, directory, up_axis, height, robot_radius=0.0, known_fraction=0.5):
         """`occupancy_slice` written as `directory`/occupancy.pgm and occupancy.yaml (save_map); returns the slice."""
         grid = self.occupancy_slice(up_axis, height, robot_radius, known_fraction)
@@ -656,7 +761,10 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
     {output}/metrics_tsdf_clearance.txt (trajectory_clearance; `tsdf_clearance_min_m`, `tsdf_clearance_inside` and
     `tsdf_clearance_unknown` in `stats`), with save_volume {output}/mesh/tsdf_esdf.npz (dist, state, lo, voxel), and with
     slice = {up_axis, height, robot_radius, known_fraction} the map {output}/map/occupancy.pgm and occupancy.yaml
-    (ESDF.save_map).  Returns the Mesh, or None when the key is absent or disabled."""
+    (ESDF.save_map), and with plan = {enable, robot_radius, allow_unknown, snap, start, goal} (absent by default; start
+    and goal are world points or "last" / "first", the run's last and first camera centre, by default "last" and "first":
+    the way home) the route of ESDF.plan into {output}/map/path.txt (plan.path_text; `tsdf_path_reachable` and
+    `tsdf_path_length_m` in `stats`).  Returns the Mesh, or None when the key is absent or disabled."""
     opt = slam.cfg.get("tsdf") or {}
     if not opt.get("enable", False):
         return None
@@ -694,6 +802,24 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
         if sl:
             field.save_map(f"{slam.output}/map", sl["up_axis"], sl["height"], sl.get("robot_radius", 0.0),
                            sl.get("known_fraction", 0.5))
+        pl = ed.get("plan") or {}
+        if pl.get("enable", False):
+            ends = []
+            for end in (pl.get("start", "last"), pl.get("goal", "first")):
+                if end in ("last", "first"):
+                    if len(c2w_list) == 0:
+                        raise ValueError("fuse_from_config: tsdf.esdf.plan needs a camera pose for 'last' / 'first'")
+                    end = torch.as_tensor(c2w_list[-1 if end == "last" else 0])[:3, 3]
+                ends.append(end)
+            res = field.plan(ends[0], ends[1], robot_radius=pl.get("robot_radius", 0.0),
+                             allow_unknown=pl.get("allow_unknown", False), snap=pl.get("snap", 0.0))
+            os.makedirs(f"{slam.output}/map", exist_ok=True)
+            with open(f"{slam.output}/map/path.txt", "w") as fh:
+                fh.write(_plan.path_text(res))
+            if stats is not None:
+                stats.update(tsdf_path_reachable=res["reachable"], tsdf_path_length_m=res["length_m"])
+            print(f"TSDF path: reachable {res['reachable']!r}, length_m {res['length_m']!r}, "
+                  f"min_clearance_m {res['min_clearance_m']!r}, {int(res['cells'].shape[0])} points")
     meshing = slam.cfg.get("meshing") or {}
     gt_path = meshing.get("gt_mesh_path") or ""
     if meshing.get("eval_rec") and gt_path.find(".ply") > -1 and os.path.exists(gt_path) and len(mesh.faces) > 0:

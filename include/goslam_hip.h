@@ -400,6 +400,54 @@ int gs_esdf_query(const float* dist, const unsigned char* state, int nx, int ny,
 int gs_esdf_slice(const unsigned char* state, const int* d2, const float* dist, int nx, int ny, int nz, int up_axis,
                   int k0, int k1, int occ_d2, int min_known, unsigned char* cells, float* clearance, gs_stream_t stream);
 
+/* ---- Cost-to-go field and paths over a passability lattice (no counterpart in the reference), csrc/geodesic.hip;
+ *      tests/geodesic_restatement.py restates it serially ----
+ *
+ * The lattice is n0 x n1 x n2, the last axis contiguous, each size in [1, 1024] (a 2-D map [n_u,n_v] is the lattice
+ * [1,n_u,n_v]), 64-bit offsets.  passable u8: non-zero where the robot's centre may be.  Bad sizes, ranges or NULL
+ * pointers return GS_ERR_INVALID_ARG before anything is launched; every entry point enqueues on the stream and reads
+ * nothing back.
+ *
+ * Moves: the 26 neighbours (d0,d1,d2) in {-1,0,1}^3 without 0, indexed in that nesting order (d0 outermost, d2
+ *   innermost; move 0 is (-1,-1,-1), move 25 is (1,1,1)).  Weight by the number of non-zero components, in milli-voxels:
+ *   1000, 1414, 1732 for 1, 2, 3.  A move from c to c + d is allowed only if every cell of the axis-aligned box spanned
+ *   by c and c + d (2, 4 or 8 cells, both ends included) lies inside the lattice and is passable: no corner is cut, and
+ *   the rule is symmetric in its ends.
+ * cost i32 [n0,n1,n2], every element written: 0 at a passable seed; elsewhere the minimum over paths of allowed moves
+ *   from any seed of the summed weights if that is <= max_cost, else GS_GEO_INF.  max_cost in [0, GS_GEO_INF - 1732]: no
+ *   candidate neighbour + w overflows, and one above max_cost is never stored.  Prefixes of a shortest path are shortest
+ *   paths and weights are positive, so the capped field is the uncapped one with every value above max_cost replaced by
+ *   GS_GEO_INF.  The field is the least fixed point of cost[c] = min(cost[c], cost[n] + w) over allowed moves, and it is
+ *   unique: the result does not depend on the order or the number of relaxations, only that none is left.
+ *
+ * gs_geodesic_brick: the relaxation's brick (b0, b1, b2); flags are u8 [2][ceil(n0/b0) * ceil(n1/b1) * ceil(n2/b2)],
+ *   gs_geodesic_flags_bytes gives that size (0 for sizes outside [1, 1024]).  The flags belong to the library between
+ *   gs_geodesic_init and the last gs_geodesic_relax of a field.
+ * gs_geodesic_init: seeds i32 [m,3], m >= 0 (NULL allowed for m == 0).  cost = GS_GEO_INF everywhere, then 0 at every
+ *   seed that is inside the lattice and passable (others are ignored, duplicates are harmless); both flag buffers
+ *   cleared, then the bricks that hold such a seed marked in buffer 0.
+ * gs_geodesic_relax: sweeps sweep0 .. sweep0 + k - 1, k >= 1, sweep0 >= 0 the number of sweeps enqueued on this field
+ *   so far (it selects the flag buffer: sweep s reads buffer s & 1 and writes the other).  changed u32 [k]: entry s is
+ *   non-zero iff sweep sweep0 + s lowered any cell.  One zero entry proves the fixed point; sweeps after it do nothing.
+ *   The number of sweeps a field needs may differ between runs; the field does not.
+ * gs_geodesic_path: start i32[3] by value, max_len >= 1, out_cells i32 [max_len,3], out_n i32 [1].  out_n = 0 when
+ *   start lies outside the lattice or holds GS_GEO_INF.  Otherwise out_cells[0] = start, and each step goes to the allowed
+ *   neighbour with the smallest cost[n] + w among those with cost[n] < GS_GEO_INF, ties to the lowest move index (at the
+ *   fixed point that smallest value is cost[cur]).  The walk ends on a cell of cost 0, which is included; out_n is the
+ *   number of cells.  out_n = -1 when max_len cells do not suffice or no such neighbour exists (a field off its fixed
+ *   point).  At the fixed point a finite non-zero cell has a neighbour at least 1000 lower: cost / 1000 + 1 cells
+ *   suffice.                                                                                                      */
+#define GS_GEO_INF 0x3fffffff
+#define GS_GEO_MAX_COST (GS_GEO_INF - 1732)
+int gs_geodesic_brick(int* b0, int* b1, int* b2);
+size_t gs_geodesic_flags_bytes(int n0, int n1, int n2);
+int gs_geodesic_init(const unsigned char* passable, int n0, int n1, int n2, const int* seeds, int m, int* cost,
+                     unsigned char* flags, gs_stream_t stream);
+int gs_geodesic_relax(const unsigned char* passable, int n0, int n1, int n2, int max_cost, int* cost,
+                      unsigned char* flags, int sweep0, int k, unsigned int* changed, gs_stream_t stream);
+int gs_geodesic_path(const int* cost, const unsigned char* passable, int n0, int n1, int n2, int start0, int start1,
+                     int start2, int max_len, int* out_cells, int* out_n, gs_stream_t stream);
+
 /* ---- frame preprocessing of the dataset readers (src/datasets.py:96-143, 565-605), csrc/frame_prep.hip ----
  *
  * Semantics: tests/frame_prep_restatement.py, bit for bit (cv2.remap / cv2.resize INTER_LINEAR on 8-bit data,
