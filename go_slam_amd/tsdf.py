@@ -21,6 +21,10 @@ csrc/geodesic.hip answers where to go: `ESDF.passable` marks the lattice points 
 `ESDF.plan` finds the shortest collision-free route between two world points and `ESDF.reachable` what can be reached
 at all (plan.py: the cost-to-go field and the walk down it; tests/geodesic_restatement.py).
 
+csrc/frontier.hip answers what has not been seen: `ESDF.frontiers` groups the free lattice points that border
+never-observed space into clusters, each priced by the route to it, and `ESDF.explore` picks one and plans the way there
+(frontier.py: marking, labelling and the cluster table; tests/frontier_restatement.py).
+
 tsdf_live.py keeps such a volume during a run, while the poses still move; it fuses through
 `keyframe_observations`, the rule `fuse_keyframes` applies per chunk.
 """
@@ -31,6 +35,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import frontier as _frontier
 from . import plan as _plan
 from .lietorch_shim import SE3
 from .neus.mesh import Mesh, marching_cubes
@@ -477,6 +482,75 @@ class ESDF:
         field = _plan.geodesic_field(passable, np.array(seeds, dtype=np.int32).reshape(-1, 3), max_cost)
         return field.cost < _plan.INF
 
+    @torch.no_grad()
+    def frontiers(self, robot_radius=0.0, start=None, snap=0.0, max_cost_m=None, min_cells=1):
+        """Where this field's free space ends in never-observed space: the `frontier.FrontierClusters` of `state` with
+        `open` = `passable(robot_radius)`, the cells the robot's centre may be.  With `start` (a world point, placed like
+        `plan`'s endpoints: its nearest lattice point, moved by `snap` to a passable cell) one `plan.geodesic_field`
+        seeded at the start's cell prices every cluster; routes longer than `max_cost_m` count as none.  World-space
+        extras on the result: `.centroid` float64 [K,3] = lo + centroid_cells * voxel, `.area_m2` float64 [K] = faces *
+        voxel^2, `.cost_m` float64 [K] = best_cost * voxel / 1000, inf where INF, `.keep` bool [K] = size >= min_cells,
+        `.start_cell` (None without a start or when no passable cell was found) and `.field` (the GeodesicField or
+        None).  Host reads: those of `frontier_clusters` and of `geodesic_field`, and the small one of `snap_cell`.
+        ValueError (plan_arguments; min_cells < 1) before the device is touched."""
+        what = "ESDF.frontiers"
+        cells, snap_cells, max_cost = self.plan_arguments([] if start is None else [start], robot_radius, snap,
+                                                          max_cost_m, what)
+        min_cells = _frontier._min_cells(min_cells, what)
+        passable = self.passable(robot_radius)
+        s = _plan.snap_cell(passable, cells[0], snap_cells) if cells else None
+        field = None if s is None else _plan.geodesic_field(passable, [s], max_cost)
+        out = _frontier.frontier_clusters(self.state, passable, None if field is None else field.cost)
+        lo = torch.tensor(self.lo, dtype=torch.float64, device=out.device)
+        out.centroid = lo[None, :] + out.centroid_cells() * self.voxel
+        out.area_m2 = out.faces.double() * self.voxel ** 2
+        out.cost_m = torch.where(out.best_cost >= _frontier.INF, math.inf, out.best_cost.double() * self.voxel / 1000.0)
+        out.keep = out.size >= min_cells
+        out.start_cell, out.field = s, field
+        return out
+
+    @torch.no_grad()
+    def explore(self, start, robot_radius=0.0, snap=0.0, max_cost_m=None, min_cells=1, order="nearest"):
+        """Where to go next from the world point `start` to see something new: `frontiers(...)`, then among the kept
+        clusters a route leads to, `order` "nearest" takes the smallest best_cost, ties to the lowest root, "largest" the
+        largest faces, then the smallest best_cost, then the lowest root; the route is the field's path from the
+        cluster's best_cell, reversed so that it reads start to goal.  -> `plan`'s dict {"reachable", "cells", "points",
+        "length_m", "min_clearance_m", "start_cell", "goal_cell", "sweeps" (the field's)} plus "cluster" (the id or
+        None), "n_clusters", "n_kept", "n_reachable" and "clusters" (the FrontierClusters of `frontiers`); when no
+        cluster qualifies, `plan`'s unreachable shape.  One read of the table's columns besides those of `frontiers`
+        and `plan`."""
+        if order not in _frontier.ORDERS:
+            raise ValueError(f"ESDF.explore: order must be one of {_frontier.ORDERS} (got {order!r})")
+        self.plan_arguments([start], robot_radius, snap, max_cost_m, "ESDF.explore")      # a start is needed here
+        fc = self.frontiers(robot_radius, start, snap, max_cost_m, min_cells)
+        dev = self.device
+        out = {"reachable": False, "cells": torch.zeros((0, 3), dtype=torch.int32, device=dev),
+               "points": torch.zeros((0, 3), dtype=torch.float64, device=dev), "length_m": math.inf,
+               "min_clearance_m": math.nan, "start_cell": fc.start_cell, "goal_cell": None,
+               "sweeps": 0 if fc.field is None else fc.field.sweeps, "cluster": None, "n_clusters": fc.n_clusters,
+               "n_kept": 0, "n_reachable": 0, "clusters": fc}
+        if fc.n_clusters == 0:
+            return out
+        cols = torch.stack([fc.best_cost.long(), fc.faces.long(), fc.root.long(), fc.keep.long(),
+                            fc.best_cell.long()]).cpu().tolist()                                        # one read
+        best_cost, faces, root, keep, best_cell = cols
+        out["n_kept"] = sum(keep)
+        out["n_reachable"] = sum(1 for k, c in zip(keep, best_cost) if k and c < _frontier.INF)
+        row = _frontier.choose(best_cost, faces, root, keep, order)
+        if row is None or fc.field is None:
+            return out
+        n1, n2 = self.dims[1], self.dims[2]
+        goal = [best_cell[row] // (n1 * n2), best_cell[row] // n2 % n1, best_cell[row] % n2]
+        cells = torch.flip(fc.field.path(goal), dims=[0]).contiguous()
+        if int(cells.shape[0]) == 0:
+            return out
+        idx = cells.long()
+        lo = torch.tensor(self.lo, dtype=torch.float64, device=dev)
+        clearance = float(self.dist[idx[:, 0], idx[:, 1], idx[:, 2]].min().item())
+        out.update(reachable=True, cells=cells, points=lo[None, :] + cells.double() * self.voxel,
+                   length_m=best_cost[row] * self.voxel / 1000.0, min_clearance_m=clearance, goal_cell=goal, cluster=row)
+        return out
+
     def save_map(self, directory, up_axis, height, robot_radius=0.0, known_fraction=0.5):
         """`occupancy_slice` written as `directory`/occupancy.pgm and occupancy.yaml (save_map); returns the slice."""
         grid = self.occupancy_slice(up_axis, height, robot_radius, known_fraction)
@@ -764,7 +838,12 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
     (ESDF.save_map), and with plan = {enable, robot_radius, allow_unknown, snap, start, goal} (absent by default; start
     and goal are world points or "last" / "first", the run's last and first camera centre, by default "last" and "first":
     the way home) the route of ESDF.plan into {output}/map/path.txt (plan.path_text; `tsdf_path_reachable` and
-    `tsdf_path_length_m` in `stats`).  Returns the Mesh, or None when the key is absent or disabled."""
+    `tsdf_path_length_m` in `stats`), and with frontiers = {enable, robot_radius, min_cells, start, snap, order} (absent by
+    default; start is a world point or "last", the default) the frontier clusters of ESDF.frontiers into
+    {output}/map/frontiers.txt (frontier.frontiers_text) and, when ESDF.explore finds a goal, its route into
+    {output}/map/explore_path.txt (plan.path_text; `tsdf_frontier_cells`, `tsdf_frontier_clusters`,
+    `tsdf_unknown_fraction` and `tsdf_explore_reachable` in `stats`).  Returns the Mesh, or None when the key is absent or
+    disabled."""
     opt = slam.cfg.get("tsdf") or {}
     if not opt.get("enable", False):
         return None
@@ -820,6 +899,30 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
                 stats.update(tsdf_path_reachable=res["reachable"], tsdf_path_length_m=res["length_m"])
             print(f"TSDF path: reachable {res['reachable']!r}, length_m {res['length_m']!r}, "
                   f"min_clearance_m {res['min_clearance_m']!r}, {int(res['cells'].shape[0])} points")
+        fr = ed.get("frontiers") or {}
+        if fr.get("enable", False):
+            start = fr.get("start", "last")
+            if isinstance(start, str):
+                if start != "last":
+                    raise ValueError(f"fuse_from_config: tsdf.esdf.frontiers.start is a world point or 'last' (got {start!r})")
+                if len(c2w_list) == 0:
+                    raise ValueError("fuse_from_config: tsdf.esdf.frontiers needs a camera pose for 'last'")
+                start = torch.as_tensor(c2w_list[-1])[:3, 3]
+            res = field.explore(start, robot_radius=fr.get("robot_radius", 0.0), snap=fr.get("snap", 0.0),
+                                min_cells=fr.get("min_cells", 1), order=fr.get("order", "nearest"))
+            report = _frontier.summary(res["clusters"], res["cluster"])
+            os.makedirs(f"{slam.output}/map", exist_ok=True)
+            with open(f"{slam.output}/map/frontiers.txt", "w") as fh:
+                fh.write(_frontier.frontiers_text(report))
+            if res["reachable"]:
+                with open(f"{slam.output}/map/explore_path.txt", "w") as fh:
+                    fh.write(_plan.path_text(res))
+            if stats is not None:
+                stats.update(tsdf_frontier_cells=report["n_frontier"], tsdf_frontier_clusters=report["n_clusters"],
+                             tsdf_unknown_fraction=report["unknown_fraction"], tsdf_explore_reachable=res["reachable"])
+            print(f"TSDF frontiers: {report['n_frontier']} cells in {report['n_clusters']} clusters, {report['n_kept']} "
+                  f"kept, {report['n_reachable']} reachable, unknown_fraction {report['unknown_fraction']!r}, "
+                  f"chosen {report['cluster']!r}")
     meshing = slam.cfg.get("meshing") or {}
     gt_path = meshing.get("gt_mesh_path") or ""
     if meshing.get("eval_rec") and gt_path.find(".ply") > -1 and os.path.exists(gt_path) and len(mesh.faces) > 0:

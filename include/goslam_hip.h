@@ -448,6 +448,63 @@ int gs_geodesic_relax(const unsigned char* passable, int n0, int n1, int n2, int
 int gs_geodesic_path(const int* cost, const unsigned char* passable, int n0, int n1, int n2, int start0, int start1,
                      int start2, int max_len, int* out_cells, int* out_n, gs_stream_t stream);
 
+/* ---- Frontiers of a state lattice: free cells next to never-observed space, their clusters and one table row per
+ *      cluster (no counterpart in the reference), csrc/frontier.hip; tests/frontier_restatement.py restates it serially
+ *       ----
+ *
+ * The lattice is n0 x n1 x n2, the last axis contiguous, each size in [1, 1024] (a 2-D map [n_u,n_v] is the lattice
+ * [1,n_u,n_v]): a linear index ((c0 * n1) + c1) * n2 + c2 fits in 30 bits.  state u8: 0 unknown, 1 free, any other value
+ * solid (gs_esdf_build writes 2).  open u8 or NULL: non-zero where a frontier cell may be (NULL: everywhere).  cost i32 or
+ * NULL: a gs_geodesic_* field over the same lattice, GS_GEO_INF where unreachable.  Everything is integer.  Bad sizes,
+ * ranges or NULL where a pointer is needed return GS_ERR_INVALID_ARG before anything is launched; every entry point
+ * enqueues on the stream and reads nothing back.
+ *
+ * Frontier cell: state == 1, open == NULL || open != 0, and at least one of the 6 face neighbours lies inside the lattice
+ *   and has state == 0.  The lattice's own border is not unknown.
+ * Clusters: the connected components of the frontier cells under 26-connectivity (the neighbours (d0,d1,d2) in
+ *   {-1,0,1}^3 without 0).  label i32: -1 off the frontier, else the smallest linear index in the cell's component.  It is
+ *   the fixed point of label[c] = min(label[c], label[n]) over frontier neighbours n, started from label = own index,
+ *   and it is unique: the result does not depend on the order or the number of relaxations, only that none is left.
+ * Table: K rows, one per cluster, ascending root; the row number is the cluster's id.
+ *     root i32 [K]      the cluster's label
+ *     size i32 [K]      its number of cells
+ *     faces i32 [K]     the number of pairs (cell of the cluster, face neighbour inside the lattice with state == 0)
+ *     sum i64 [K,3]     the sums of the cells' coordinates (c0, c1, c2)
+ *     bbox i32 [K,6]    (min c0, min c1, min c2, max c0, max c1, max c2)
+ *     best i32 [K,2]    8-byte aligned; row r read as one little-endian u64 is the minimum over the cluster's cells of
+ *                       (cost << 32) | linear index, so [r][0] = best_cell, the cheapest cell, ties to the lowest index,
+ *                       and [r][1] = best_cost.  cost == NULL counts as GS_GEO_INF everywhere: best_cell is the root.
+ *
+ * gs_frontier_brick: the relaxation's brick (b0, b1, b2); flags are u8 [2][ceil(n0/b0) * ceil(n1/b1) * ceil(n2/b2)],
+ *   gs_frontier_flags_bytes gives that size (0 for sizes outside [1, 1024]).  The flags belong to the library between
+ *   gs_frontier_mark and the last gs_frontier_relax of a lattice.
+ * gs_frontier_mark: frontier u8 (0 / 1) and label (own index / -1), every element written; counts u32 [4] = the number
+ *   of unknown, free, solid and frontier cells; both flag buffers cleared, then the bricks that hold a frontier cell
+ *   marked in buffer 0.
+ * gs_frontier_relax: sweeps sweep0 .. sweep0 + k - 1, k >= 1, sweep0 >= 0 the number of sweeps enqueued on these labels
+ *   so far (sweep s reads flag buffer s & 1 and writes the other).  changed u32 [k]: entry s is non-zero iff sweep
+ *   sweep0 + s lowered any label.  One zero entry proves the fixed point; sweeps after it do nothing.  The number of
+ *   sweeps may differ between runs; the labels do not.
+ * gs_frontier_roots: counts the roots (label == own index) per block of cells and scans the counts into the workspace
+ *   (gs_frontier_workspace_bytes; 0 for sizes outside [1, 1024]); n_roots i32 [1] = K, which the caller reads to size the
+ *   table.
+ * gs_frontier_table: rows = K as read from gs_frontier_roots of the same labels and workspace, capacity = the number of
+ *   rows the table's arrays hold; 0 <= rows <= capacity, else GS_ERR_INVALID_ARG.  rows == 0 launches nothing.  Rows
+ *   [0, rows) of every column are written.  (With rows below the true K the roots past the table and their clusters are
+ *   left out; nothing is written outside [0, rows).)                                                                  */
+int gs_frontier_brick(int* b0, int* b1, int* b2);
+size_t gs_frontier_flags_bytes(int n0, int n1, int n2);
+size_t gs_frontier_workspace_bytes(int n0, int n1, int n2);
+int gs_frontier_mark(const unsigned char* state, const unsigned char* open, int n0, int n1, int n2,
+                     unsigned char* frontier, int* label, unsigned int* counts, unsigned char* flags, gs_stream_t stream);
+int gs_frontier_relax(int n0, int n1, int n2, int* label, unsigned char* flags, int sweep0, int k, unsigned int* changed,
+                      gs_stream_t stream);
+int gs_frontier_roots(const int* label, int n0, int n1, int n2, void* workspace, size_t workspace_bytes, int* n_roots,
+                      gs_stream_t stream);
+int gs_frontier_table(const unsigned char* state, const int* label, const int* cost, int n0, int n1, int n2,
+                      const void* workspace, size_t workspace_bytes, int rows, int capacity, int* root, int* size,
+                      int* faces, long long* sum, int* bbox, int* best, gs_stream_t stream);
+
 /* ---- frame preprocessing of the dataset readers (src/datasets.py:96-143, 565-605), csrc/frame_prep.hip ----
  *
  * Semantics: tests/frame_prep_restatement.py, bit for bit (cv2.remap / cv2.resize INTER_LINEAR on 8-bit data,
