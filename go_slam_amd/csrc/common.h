@@ -278,6 +278,29 @@ __device__ __forceinline__ double gs_wave_sum_f64(double v) {
   return v;
 }
 
+// integer butterflies: every lane returns the wave's sum / minimum
+__device__ __forceinline__ int gs_wave_sum_i32(int v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, GS_WAVE);
+  return v;
+}
+__device__ __forceinline__ int gs_wave_min_i32(int v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const int o = __shfl_xor(v, off, GS_WAVE);
+    v = o < v ? o : v;
+  }
+  return v;
+}
+__device__ __forceinline__ unsigned long long gs_wave_min_u64(unsigned long long v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long o = __shfl_xor(v, off, GS_WAVE);
+    v = o < v ? o : v;
+  }
+  return v;
+}
+
 __device__ __forceinline__ void gs_atomic_add_f64(double* p, double v) {
   // global_atomic_add_f64 (hardware fp64 atomic on gfx950), relaxed, device scope
   __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -5,23 +5,18 @@
 // frontier_mark_kernel: one lane per cell, FR_PER cells per lane, runs along the last axis coalesced.  Writes frontier,
 //   label (own index on the frontier, -1 off it) and the four counts (ballots per wave, LDS per workgroup, at most four
 //   integer atomics per workgroup), and sets the dirty byte, in flag buffer 0, of every brick that holds a frontier cell.
-// gs_frontier_relax enqueues k launches of frontier_relax_kernel, the pattern of geodesic_relax_kernel: one workgroup
-//   per brick of B0 x B1 x B2 cells; a brick whose dirty flag is clear leaves after one byte load.  A dirty one loads the
-//   labels of the brick and a one-cell halo into LDS (-1, as unsigned the largest value, where there is no frontier cell
-//   or no lattice), takes label[label[c]] where that is lower (FRONTIER_SHORTCUT), and lowers every cell to the smallest
-//   of its 26 neighbours inside LDS until a round lowers nothing or FR_ROUNDS rounds have run.  Only lowered cells are
-//   written back.  A brick that lowered a cell on a face, edge or corner marks the bricks behind it in the next sweep's
-//   flag buffer, marks itself when it ran out of rounds, and stores 1 to changed[s]; every such store writes the same
-//   value, so none is atomic.  It clears its own byte of the buffer it read.
-// Labels are relaxed in place and nothing waits for another workgroup: a value read while its owner lowers it is stale,
-// which is still the index of a cell of the same component and only postpones the improvement to the next sweep.
-// Values only fall, so the fixed point -- every cell holds its component's smallest index -- is reached whatever the
-// order.
+// gs_frontier_relax enqueues k launches of frontier_relax_kernel, the brick sweep of brick_relax.h with FrRule: a tile
+//   entry is the label as unsigned (-1, the largest value, where there is no frontier cell or no lattice), a cell first
+//   takes label[label[c]] where that is lower (FRONTIER_SHORTCUT), and is lowered to the smallest of its 26 neighbours.
+// Every stored label is the index of a cell of the same component: a cell starts with its own index and is only ever
+// given a label that a neighbour, or the cell its label names, holds or held -- a stale one included.  Labels only
+// fall, so the fixed point -- every cell holds its component's smallest index -- is reached whatever the order
+// (brick_relax.h).
 // Table: the roots (label == own index) are compacted in ascending order by count / scan / emit launches over blocks of
 // FR_THREADS * FR_PER cells; emit also clears the row.  frontier_table_kernel passes over the cells once: a frontier
 // cell finds its row by binary search of its label among the roots, the lanes of a wave that share a row reduce their
 // contributions by butterflies, and one lane per (wave, row) issues the integer atomics.  No scratch, no floating point.
-#include "common.h"
+#include "brick_relax.h"
 
 namespace {
 
@@ -36,23 +31,15 @@ namespace {
 #ifndef FRONTIER_SHORTCUT     // 0: neighbour relaxation alone (tools/frontier_bench.py counts the sweeps of both)
 #define FRONTIER_SHORTCUT 1
 #endif
-constexpr int B0 = FRONTIER_B0, B1 = FRONTIER_B1, B2 = FRONTIER_B2;
-constexpr int FR_THREADS = 256;
+using FrBrick = Brick<FRONTIER_B0, FRONTIER_B1, FRONTIER_B2, FRONTIER_ROUNDS_MAX>;
+constexpr int B0 = FrBrick::B0, B1 = FrBrick::B1, B2 = FrBrick::B2;
+constexpr int FR_THREADS = FrBrick::THREADS;
 constexpr int FR_WAVES = FR_THREADS / GS_WAVE;
-constexpr int FR_CELLS = B0 * B1 * B2;
-constexpr int FR_OWN = FR_CELLS / FR_THREADS;              // cells per lane of the relax kernel
-constexpr int T0 = B0 + 2, T1 = B1 + 2, T2 = B2 + 2;       // the tile: the brick and its halo
-constexpr int FR_TILE = T0 * T1 * T2;
-constexpr int FR_ROUNDS = FRONTIER_ROUNDS_MAX;
-constexpr int FR_MAX = 1024;                               // cells per axis
+constexpr int FR_MAX = BRICK_MAX_CELLS;                    // cells per axis
 constexpr int FR_PER = 8;                                  // cells per lane of the lattice-wide passes
 constexpr int FR_BLOCK = FR_THREADS * FR_PER;              // cells per workgroup of those passes
 constexpr int FR_SCAN_THREADS = 1024;
 constexpr unsigned FR_NONE = 0xffffffffu;                  // label -1
-static_assert(FR_CELLS % FR_THREADS == 0, "a lane owns a whole number of cells");
-
-__host__ __device__ constexpr int fr_nb(int m) { return m < 13 ? m : m + 1; }      // neighbour m of 26, centre skipped
-__host__ __device__ constexpr int fr_tile_offset(int e0, int e1, int e2) { return (e0 * T1 + e1) * T2 + e2; }
 
 __device__ __forceinline__ int fr_popc(unsigned long long b) { return __popcll(b); }
 
@@ -113,107 +100,45 @@ __global__ __launch_bounds__(FR_THREADS) void frontier_mark_kernel(const unsigne
   }
 }
 
-__global__ __launch_bounds__(FR_THREADS) void frontier_relax_kernel(int* label, int n0, int n1, int n2, int nb0, int nb1,
-                                                                    int nb2, unsigned char* cur, unsigned char* next,
-                                                                    unsigned int* changed) {
-  __shared__ unsigned tile[FR_TILE];
-  __shared__ int lowered[3];                                // round r stores to [r % 3]
-  __shared__ int face[6];                                   // a cell with index 0 / B - 1 along axis a fell: [2a] / [2a + 1]
-  const int tid = threadIdx.x;
-  const int brick = blockIdx.x;
-  if (cur[brick] == 0) return;                              // written before this launch: every lane reads the same
-  const int i2 = brick % nb2, i1 = brick / nb2 % nb1, i0 = brick / nb2 / nb1;
-  const int base0 = i0 * B0 - 1, base1 = i1 * B1 - 1, base2 = i2 * B2 - 1;     // the tile's corner, a halo cell
-
-  if (tid < 3) lowered[tid] = 0;
-  if (tid < 6) face[tid] = 0;
-  for (int q = tid; q < FR_TILE; q += FR_THREADS) {
-    const int t0 = q / (T1 * T2), r = q - t0 * (T1 * T2), t1 = r / T2, t2 = r - t1 * T2;
-    const int g0 = base0 + t0, g1 = base1 + t1, g2 = base2 + t2;
-    const bool inside = g0 >= 0 && g0 < n0 && g1 >= 0 && g1 < n1 && g2 >= 0 && g2 < n2;
-    const size_t at = inside ? ((size_t)g0 * n1 + g1) * n2 + g2 : 0;
+struct FrRule {
+  using Value = unsigned;
+  struct Cell {};
+  int* label;
+  unsigned ncells;
+  __device__ __forceinline__ unsigned load(size_t at, bool inside, int) const {
     const unsigned v = (unsigned)label[at];
-    tile[q] = inside ? v : FR_NONE;
+    return inside ? v : FR_NONE;
   }
-  __syncthreads();
-  if (tid == 0) cur[brick] = 0;                             // after the barrier: every wave has read the flag
-
-  int at[FR_OWN];
-  unsigned val[FR_OWN], was[FR_OWN];
-#pragma unroll
-  for (int j = 0; j < FR_OWN; ++j) {
-    const int q = tid + FR_THREADS * j;
-    const int z = q % B2, y = q / B2 % B1, x = q / (B1 * B2);
-    at[j] = fr_tile_offset(x + 1, y + 1, z + 1);
-    val[j] = was[j] = tile[at[j]];                          // FR_NONE off the frontier and outside the lattice
+  __device__ __forceinline__ unsigned prepare(unsigned* tile, int at, unsigned v, Cell&) const {
 #if FRONTIER_SHORTCUT
-    if (val[j] < (unsigned)(n0 * n1 * n2)) {
-      // the label of the cell this one points at: possibly stale, always an index of this component at most val[j]
-      const unsigned far = (unsigned)label[val[j]];
-      if (far < val[j]) {
-        val[j] = far;
-        tile[at[j]] = far;                                  // a neighbour reads the old or the new value: both are valid
+    if (v < ncells) {
+      // the label of the cell this one points at: possibly stale, always an index of this component at most v
+      const unsigned far = (unsigned)label[v];
+      if (far < v) {
+        tile[at] = far;                                     // a neighbour reads the old or the new value: both are valid
+        return far;
       }
     }
 #endif
+    return v;                                               // FR_NONE off the frontier and outside the lattice
   }
-
-  int round = 0;
-  bool more;
-  do {
-    bool fell = false;
+  __device__ __forceinline__ bool active(unsigned v, const Cell&) const { return v != FR_NONE; }
+  __device__ __forceinline__ unsigned lower(const unsigned* tile, int at, unsigned v, const Cell&) const {
+    unsigned best = v;
 #pragma unroll
-    for (int j = 0; j < FR_OWN; ++j) {
-      if (val[j] == FR_NONE) continue;
-      unsigned best = val[j];
-#pragma unroll
-      for (int m = 0; m < 26; ++m) {
-        const unsigned cand = tile[at[j] + fr_tile_offset(fr_nb(m) / 9 - 1, fr_nb(m) / 3 % 3 - 1, fr_nb(m) % 3 - 1)];
-        best = cand < best ? cand : best;                   // FR_NONE never wins
-      }
-      if (best < val[j]) {
-        val[j] = best;
-        tile[at[j]] = best;
-        fell = true;
-      }
+    for (int m = 0; m < 26; ++m) {
+      const unsigned cand = tile[at + FrBrick::nb_offset(m)];
+      best = cand < best ? cand : best;                     // FR_NONE never wins
     }
-    if (fell) lowered[round % 3] = 1;
-    __syncthreads();
-    more = lowered[round % 3] != 0;
-    if (tid == 0) lowered[(round + 2) % 3] = 0;             // last read before this barrier, next written after the next
-    ++round;
-  } while (more && round < FR_ROUNDS);
+    return best;
+  }
+  __device__ __forceinline__ void store(size_t at, unsigned v) const { label[at] = (int)v; }
+};
 
-  bool any = false;
-#pragma unroll
-  for (int j = 0; j < FR_OWN; ++j) {
-    if (val[j] >= was[j]) continue;
-    const int q = tid + FR_THREADS * j;
-    const int z = q % B2, y = q / B2 % B1, x = q / (B1 * B2);
-    label[((size_t)(base0 + 1 + x) * n1 + (base1 + 1 + y)) * n2 + (base2 + 1 + z)] = (int)val[j];   // inside: was != NONE
-    any = true;
-    if (x == 0) face[0] = 1;
-    if (x == B0 - 1) face[1] = 1;
-    if (y == 0) face[2] = 1;
-    if (y == B1 - 1) face[3] = 1;
-    if (z == 0) face[4] = 1;
-    if (z == B2 - 1) face[5] = 1;
-  }
-  if (any) lowered[round % 3] = 1;                          // zero since the barrier before last, not read since
-  __syncthreads();
-  if (lowered[round % 3] == 0) return;
-  if (tid == 0) changed[0] = 1;
-  if (tid < 27) {
-    const int d0 = tid / 9 - 1, d1 = tid / 3 % 3 - 1, d2 = tid % 3 - 1;
-    const int j0 = i0 + d0, j1 = i1 + d1, j2 = i2 + d2;
-    // a lowered cell that the brick at +d reads lies on every face d names, so all of them are set (the converse need
-    // not hold: a brick marked in vain loads its tile, lowers nothing and marks nobody)
-    bool mark = (d0 == 0 || face[d0 < 0 ? 0 : 1] != 0) && (d1 == 0 || face[d1 < 0 ? 2 : 3] != 0) &&
-                (d2 == 0 || face[d2 < 0 ? 4 : 5] != 0);
-    if (tid == 13) mark = more;                             // itself: only when the rounds ran out
-    if (mark && j0 >= 0 && j0 < nb0 && j1 >= 0 && j1 < nb1 && j2 >= 0 && j2 < nb2)
-      next[((size_t)j0 * nb1 + j1) * nb2 + j2] = 1;
-  }
+__global__ __launch_bounds__(FR_THREADS) void frontier_relax_kernel(int* label, int n0, int n1, int n2, int nb0, int nb1,
+                                                                    int nb2, unsigned char* cur, unsigned char* next,
+                                                                    unsigned int* changed) {
+  brick_relax<FrBrick>(FrRule{label, (unsigned)(n0 * n1 * n2)}, n0, n1, n2, nb0, nb1, nb2, cur, next, changed);
 }
 
 // Which of this lane's FR_PER cells of block `base` are roots, each one's rank among the block's roots in ascending cell
@@ -314,28 +239,6 @@ __global__ __launch_bounds__(FR_THREADS) void frontier_emit_kernel(const int* __
   }
 }
 
-__device__ __forceinline__ int fr_wave_sum(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, GS_WAVE);
-  return v;
-}
-__device__ __forceinline__ int fr_wave_min(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const int o = __shfl_xor(v, off, GS_WAVE);
-    v = o < v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ unsigned long long fr_wave_min(unsigned long long v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const unsigned long long o = __shfl_xor(v, off, GS_WAVE);
-    v = o < v ? o : v;
-  }
-  return v;
-}
-
 __global__ __launch_bounds__(FR_THREADS) void frontier_table_kernel(
     const unsigned char* __restrict__ state, const int* __restrict__ label, const int* __restrict__ cost, int n0, int n1,
     int n2, const int* __restrict__ root, int rows, int* size, int* faces, unsigned long long* sum, int* bbox,
@@ -369,13 +272,14 @@ __global__ __launch_bounds__(FR_THREADS) void frontier_table_kernel(
       const bool mine = id == row;
       const unsigned long long members = __ballot(mine);
       todo &= ~members;
-      const int f = fr_wave_sum(mine ? nf : 0);
-      const int s0 = fr_wave_sum(mine ? c0 : 0), s1 = fr_wave_sum(mine ? c1 : 0), s2 = fr_wave_sum(mine ? c2 : 0);
-      const int lo0 = fr_wave_min(mine ? c0 : FR_MAX), lo1 = fr_wave_min(mine ? c1 : FR_MAX);
-      const int lo2 = fr_wave_min(mine ? c2 : FR_MAX);
-      const int hi0 = -fr_wave_min(mine ? -c0 : 1), hi1 = -fr_wave_min(mine ? -c1 : 1);
-      const int hi2 = -fr_wave_min(mine ? -c2 : 1);
-      const unsigned long long k = fr_wave_min(mine ? key : ~0ull);
+      const int f = gs_wave_sum_i32(mine ? nf : 0);
+      const int s0 = gs_wave_sum_i32(mine ? c0 : 0), s1 = gs_wave_sum_i32(mine ? c1 : 0);
+      const int s2 = gs_wave_sum_i32(mine ? c2 : 0);
+      const int lo0 = gs_wave_min_i32(mine ? c0 : FR_MAX), lo1 = gs_wave_min_i32(mine ? c1 : FR_MAX);
+      const int lo2 = gs_wave_min_i32(mine ? c2 : FR_MAX);
+      const int hi0 = -gs_wave_min_i32(mine ? -c0 : 1), hi1 = -gs_wave_min_i32(mine ? -c1 : 1);
+      const int hi2 = -gs_wave_min_i32(mine ? -c2 : 1);
+      const unsigned long long k = gs_wave_min_u64(mine ? key : ~0ull);
       if (lane == leader) {
         atomicAdd(&size[row], fr_popc(members));
         atomicAdd(&faces[row], f);
@@ -394,9 +298,6 @@ __global__ __launch_bounds__(FR_THREADS) void frontier_table_kernel(
   }
 }
 
-bool fr_dims_ok(int n0, int n1, int n2) {
-  return n0 >= 1 && n0 <= FR_MAX && n1 >= 1 && n1 <= FR_MAX && n2 >= 1 && n2 <= FR_MAX;
-}
 int fr_blocks(int n0, int n1, int n2) { return (int)(((long long)n0 * n1 * n2 + FR_BLOCK - 1) / FR_BLOCK); }     // <= 2^19
 
 }  // namespace
@@ -410,19 +311,18 @@ extern "C" int gs_frontier_brick(int* b0, int* b1, int* b2) {
 }
 
 extern "C" size_t gs_frontier_flags_bytes(int n0, int n1, int n2) {
-  if (!fr_dims_ok(n0, n1, n2)) return 0;
-  return (size_t)2 * gs_cdiv(n0, B0) * gs_cdiv(n1, B1) * gs_cdiv(n2, B2);
+  return brick_flags_bytes<FrBrick>(n0, n1, n2);
 }
 
 extern "C" size_t gs_frontier_workspace_bytes(int n0, int n1, int n2) {
-  if (!fr_dims_ok(n0, n1, n2)) return 0;
+  if (!brick_dims_ok(n0, n1, n2)) return 0;
   return 2 * gs_align(sizeof(unsigned) * (size_t)fr_blocks(n0, n1, n2));      // count and first, per block
 }
 
 extern "C" int gs_frontier_mark(const unsigned char* state, const unsigned char* open, int n0, int n1, int n2,
                                 unsigned char* frontier, int* label, unsigned int* counts, unsigned char* flags,
                                 gs_stream_t stream) {
-  GS_REQUIRE(fr_dims_ok(n0, n1, n2), "frontier_mark: lattice %d x %d x %d outside [1, 1024]", n0, n1, n2);
+  GS_REQUIRE(brick_dims_ok(n0, n1, n2), "frontier_mark: lattice %d x %d x %d outside [1, 1024]", n0, n1, n2);
   GS_REQUIRE(state && frontier && label && counts && flags, "frontier_mark: null pointer");
   const hipStream_t s = (hipStream_t)stream;
   if (hipMemsetAsync(counts, 0, sizeof(unsigned int) * 4, s) != hipSuccess ||
@@ -439,30 +339,22 @@ extern "C" int gs_frontier_mark(const unsigned char* state, const unsigned char*
 
 extern "C" int gs_frontier_relax(int n0, int n1, int n2, int* label, unsigned char* flags, int sweep0, int k,
                                  unsigned int* changed, gs_stream_t stream) {
-  GS_REQUIRE(fr_dims_ok(n0, n1, n2), "frontier_relax: lattice %d x %d x %d outside [1, 1024]", n0, n1, n2);
+  GS_REQUIRE(brick_dims_ok(n0, n1, n2), "frontier_relax: lattice %d x %d x %d outside [1, 1024]", n0, n1, n2);
   GS_REQUIRE(k >= 1 && sweep0 >= 0 && sweep0 <= 0x7fffffff - k, "frontier_relax: sweep0=%d k=%d", sweep0, k);
   GS_REQUIRE(label && flags && changed, "frontier_relax: null pointer");
   const hipStream_t s = (hipStream_t)stream;
   const int nb0 = gs_cdiv(n0, B0), nb1 = gs_cdiv(n1, B1), nb2 = gs_cdiv(n2, B2);
   const size_t nbricks = (size_t)nb0 * nb1 * nb2;           // at most 2^20 workgroups for the shipped brick
-  if (hipMemsetAsync(changed, 0, sizeof(unsigned int) * (size_t)k, s) != hipSuccess) {
-    gs_set_error("frontier_relax: clearing changed[%d] failed", k);
-    return GS_ERR_LAUNCH;
-  }
-  GS_TIMING_PRE();
-  for (int i = 0; i < k; ++i) {
-    const int parity = (sweep0 + i) & 1;
-    frontier_relax_kernel<<<(unsigned)nbricks, FR_THREADS, 0, s>>>(label, n0, n1, n2, nb0, nb1, nb2,
-                                                                   flags + parity * nbricks,
-                                                                   flags + (parity ^ 1) * nbricks, changed + i);
-    GS_CHECK_LAUNCH("frontier_relax");
-  }
-  return GS_OK;
+  return brick_relax_enqueue("frontier_relax", nbricks, flags, sweep0, k, changed, s,
+                             [&](unsigned char* cur, unsigned char* next, unsigned int* ch) {
+                               frontier_relax_kernel<<<(unsigned)nbricks, FR_THREADS, 0, s>>>(label, n0, n1, n2, nb0, nb1,
+                                                                                             nb2, cur, next, ch);
+                             });
 }
 
 extern "C" int gs_frontier_roots(const int* label, int n0, int n1, int n2, void* workspace, size_t workspace_bytes,
                                  int* n_roots, gs_stream_t stream) {
-  GS_REQUIRE(fr_dims_ok(n0, n1, n2), "frontier_roots: lattice %d x %d x %d outside [1, 1024]", n0, n1, n2);
+  GS_REQUIRE(brick_dims_ok(n0, n1, n2), "frontier_roots: lattice %d x %d x %d outside [1, 1024]", n0, n1, n2);
   GS_REQUIRE(label && workspace && n_roots, "frontier_roots: null pointer");
   GS_REQUIRE(workspace_bytes >= gs_frontier_workspace_bytes(n0, n1, n2), "frontier_roots: workspace of %zu bytes, %zu needed",
              workspace_bytes, gs_frontier_workspace_bytes(n0, n1, n2));
@@ -481,7 +373,7 @@ extern "C" int gs_frontier_roots(const int* label, int n0, int n1, int n2, void*
 extern "C" int gs_frontier_table(const unsigned char* state, const int* label, const int* cost, int n0, int n1, int n2,
                                  const void* workspace, size_t workspace_bytes, int rows, int capacity, int* root,
                                  int* size, int* faces, long long* sum, int* bbox, int* best, gs_stream_t stream) {
-  GS_REQUIRE(fr_dims_ok(n0, n1, n2), "frontier_table: lattice %d x %d x %d outside [1, 1024]", n0, n1, n2);
+  GS_REQUIRE(brick_dims_ok(n0, n1, n2), "frontier_table: lattice %d x %d x %d outside [1, 1024]", n0, n1, n2);
   GS_REQUIRE(rows >= 0 && capacity >= rows, "frontier_table: %d rows do not fit a table of capacity %d", rows, capacity);
   GS_REQUIRE(state && label && workspace && root && size && faces && sum && bbox && best, "frontier_table: null pointer");
   GS_REQUIRE(((uintptr_t)best & 7u) == 0, "frontier_table: best is not 8-byte aligned");

@@ -9,7 +9,6 @@ include/goslam_hip.h, gs_frontier_*).  `ESDF.frontiers` / 
 distance field under it and price every cluster with one `plan.geodesic_field`, `frontiers_on_map` does the same over a
 2-D occupancy map, and `frontiers_text` / `parse_frontiers` are the run's map/frontiers.txt.
 """
-import ctypes
 import math
 
 import numpy as np
@@ -20,7 +19,7 @@ from . import plan as _plan
 
 INF = _plan.INF                        # GS_GEO_INF
 MAX_CELLS = _plan.MAX_CELLS            # per axis
-SWEEP_BATCH = 8                        # sweeps enqueued per host read of `changed`
+SWEEP_BATCH = _plan.SWEEP_BATCH        # sweeps enqueued per host read of `changed`
 ORDERS = ("nearest", "largest")
 
 
@@ -74,9 +73,7 @@ def cluster_arguments(state, open=None, cost=None, max_sweeps=65536):
 
 def brick():
     """The relaxation's brick (b0, b1, b2) in cells (gs_frontier_brick)."""
-    b = [ctypes.c_int(0) for _ in range(3)]
-    _lib.check(_lib.lib().gs_frontier_brick(*[ctypes.byref(v) for v in b]), "gs_frontier_brick")
-    return tuple(v.value for v in b)
+    return _plan._brick("gs_frontier_brick")
 
 
 @torch.no_grad()
@@ -108,18 +105,10 @@ def frontier_clusters(state, open=None, cost=None, max_sweeps=65536):
         stream = _lib.stream_ptr(dev)
         _lib.check(L.gs_frontier_mark(_lib.ptr(state), _lib.ptr(open), *dims, _lib.ptr(frontier), _lib.ptr(label),
                                       _lib.ptr(counts), _lib.ptr(flags), stream), "frontier_clusters (mark)")
-        sweeps = 0
-        while True:
-            k = min(SWEEP_BATCH, max_sweeps - sweeps)
-            if k <= 0:
-                raise RuntimeError(f"frontier_clusters: no fixed point after max_sweeps = {max_sweeps} sweeps")
-            _lib.check(L.gs_frontier_relax(*dims, _lib.ptr(label), _lib.ptr(flags), sweeps, k, _lib.ptr(changed), stream),
-                       "frontier_clusters (relax)")
-            quiet = (changed[:k] == 0).cpu().tolist()                         # the batch's one read
-            if True in quiet:
-                sweeps += quiet.index(True) + 1
-                break
-            sweeps += k
+        sweeps = _plan.sweep_to_fixed_point(
+            lambda sweep0, k: _lib.check(L.gs_frontier_relax(*dims, _lib.ptr(label), _lib.ptr(flags), sweep0, k,
+                                                             _lib.ptr(changed), stream), "frontier_clusters (relax)"),
+            changed, max_sweeps, "frontier_clusters")
         _lib.check(L.gs_frontier_roots(_lib.ptr(label), *dims, _lib.ptr(ws), ws_bytes, _lib.ptr(n_roots), stream),
                    "frontier_clusters (roots)")
         K = int(n_roots.item())                                               # the read that sizes the table
@@ -135,19 +124,6 @@ def frontier_clusters(state, open=None, cost=None, max_sweeps=65536):
                                            _lib.ptr(best), stream), "frontier_clusters (table)")
     table["best_cell"], table["best_cost"] = best[:, 0], best[:, 1]
     return FrontierClusters(frontier, label, counts.long(), table, sweeps)
-
-
-def _map_cell(grid_shape, origin, res, xy, name, what):
-    try:
-        x, y = (float(v) for v in xy)
-    except (TypeError, ValueError):
-        raise ValueError(f"{what}: {name} must be (x, y) (got {xy!r})") from None
-    if not (math.isfinite(x) and math.isfinite(y)):
-        raise ValueError(f"{what}: {name} {xy!r} is not finite")
-    uv = (int(math.floor((x - origin[0]) / res)), int(math.floor((y - origin[1]) / res)))
-    if not (0 <= uv[0] < grid_shape[0] and 0 <= uv[1] < grid_shape[1]):
-        raise ValueError(f"{what}: {name} {xy!r} is cell {uv}, outside the map {list(grid_shape)}")
-    return uv
 
 
 def _min_cells(min_cells, what):
@@ -176,7 +152,7 @@ def frontiers_on_map(grid, start_xy=None, min_cells=1):
     if not res > 0:
         raise ValueError(f"{what}: resolution must be positive (got {res})")
     min_cells = _min_cells(min_cells, what)
-    start = None if start_xy is None else _map_cell(cells.shape, origin, res, start_xy, "start_xy", what)
+    start = None if start_xy is None else _plan.map_cell(cells.shape, origin, res, start_xy, "start_xy", what)
     free = cells == _plan.MAP_FREE
     state = torch.where(free, 1, torch.where(cells == _plan.MAP_UNKNOWN, 0, 2)).to(torch.uint8)[None].contiguous()
     field = None

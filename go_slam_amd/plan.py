@@ -99,11 +99,32 @@ def field_arguments(passable, seeds, max_cost=None, max_sweeps=65536):
     return dims, np.ascontiguousarray(s, dtype=np.int32), int(max_cost), int(max_sweeps)
 
 
+def _brick(fn_name):
+    b = [ctypes.c_int(0) for _ in range(3)]
+    _lib.check(getattr(_lib.lib(), fn_name)(*[ctypes.byref(v) for v in b]), fn_name)
+    return tuple(v.value for v in b)
+
+
 def brick():
     """The relaxation's brick (b0, b1, b2) in cells (gs_geodesic_brick)."""
-    b = [ctypes.c_int(0) for _ in range(3)]
-    _lib.check(_lib.lib().gs_geodesic_brick(*[ctypes.byref(v) for v in b]), "gs_geodesic_brick")
-    return tuple(v.value for v in b)
+    return _brick("gs_geodesic_brick")
+
+
+def sweep_to_fixed_point(enqueue, changed, max_sweeps, what):
+    """Brick sweeps until one lowers nothing; returns their number, that quiet one included.  `enqueue(sweep0, k)` makes
+    the C call that enqueues sweeps sweep0 .. sweep0 + k - 1 and has them write `changed[:k]` (int32 [SWEEP_BATCH] on the
+    device); sweeps go out in batches of SWEEP_BATCH and `changed` is read once per batch.  RuntimeError when
+    `max_sweeps` sweeps do not get there."""
+    sweeps = 0
+    while True:
+        k = min(SWEEP_BATCH, max_sweeps - sweeps)
+        if k <= 0:
+            raise RuntimeError(f"{what}: no fixed point after max_sweeps = {max_sweeps} sweeps")
+        enqueue(sweeps, k)
+        quiet = (changed[:k] == 0).cpu().tolist()                             # the batch's one read
+        if True in quiet:
+            return sweeps + quiet.index(True) + 1
+        sweeps += k
 
 
 @torch.no_grad()
@@ -127,18 +148,11 @@ def geodesic_field(passable, seeds, max_cost=None, max_sweeps=65536):
         stream = _lib.stream_ptr(dev)
         _lib.check(L.gs_geodesic_init(_lib.ptr(passable), *dims, _lib.ptr(seeds_d) if m else None, m, _lib.ptr(cost),
                                       _lib.ptr(flags), stream), "geodesic_field (init)")
-        sweeps = 0
-        while True:
-            k = min(SWEEP_BATCH, max_sweeps - sweeps)
-            if k <= 0:
-                raise RuntimeError(f"geodesic_field: no fixed point after max_sweeps = {max_sweeps} sweeps")
-            _lib.check(L.gs_geodesic_relax(_lib.ptr(passable), *dims, max_cost, _lib.ptr(cost), _lib.ptr(flags), sweeps,
-                                           k, _lib.ptr(changed), stream), "geodesic_field (relax)")
-            quiet = (changed[:k] == 0).cpu().tolist()                         # the batch's one read
-            if True in quiet:
-                sweeps += quiet.index(True) + 1
-                break
-            sweeps += k
+        sweeps = sweep_to_fixed_point(
+            lambda sweep0, k: _lib.check(L.gs_geodesic_relax(_lib.ptr(passable), *dims, max_cost, _lib.ptr(cost),
+                                                             _lib.ptr(flags), sweep0, k, _lib.ptr(changed), stream),
+                                         "geodesic_field (relax)"),
+            changed, max_sweeps, "geodesic_field")
     return GeodesicField(cost, passable, sweeps)
 
 
@@ -173,6 +187,21 @@ def snap_cell(passable, cell, radius_cells):
     return [lin // (dims[1] * dims[2]), lin // dims[2] % dims[1], lin % dims[2]]
 
 
+def map_cell(shape, origin, res, xy, name, what):
+    """The cell (u, v) = floor((xy - origin) / res) of the map point `xy` on a 2-D map of `shape`, or ValueError for a
+    point that is no two finite numbers or lies outside the map."""
+    try:
+        x, y = (float(v) for v in xy)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: {name} must be (x, y) (got {xy!r})") from None
+    if not (math.isfinite(x) and math.isfinite(y)):
+        raise ValueError(f"{what}: {name} {xy!r} is not finite")
+    uv = (int(math.floor((x - origin[0]) / res)), int(math.floor((y - origin[1]) / res)))
+    if not (0 <= uv[0] < shape[0] and 0 <= uv[1] < shape[1]):
+        raise ValueError(f"{what}: {name} {xy!r} is cell {uv}, outside the map {list(shape)}")
+    return uv
+
+
 @torch.no_grad()
 def plan_on_map(grid, start_xy, goal_xy, allow_unknown=False):
     """Plan on the 2-D map `grid` (the dict of `ESDF.occupancy_slice` or `load_map`: cells uint8 [n_u,n_v], origin,
@@ -191,18 +220,8 @@ def plan_on_map(grid, start_xy, goal_xy, allow_unknown=False):
     origin = [float(v) for v in grid["origin"]]
     if not res > 0:
         raise ValueError(f"{what}: resolution must be positive (got {res})")
-    ends = []
-    for name, xy in (("start_xy", start_xy), ("goal_xy", goal_xy)):
-        try:
-            x, y = (float(v) for v in xy)
-        except (TypeError, ValueError):
-            raise ValueError(f"{what}: {name} must be (x, y) (got {xy!r})") from None
-        if not (math.isfinite(x) and math.isfinite(y)):
-            raise ValueError(f"{what}: {name} {xy!r} is not finite")
-        uv = (int(math.floor((x - origin[0]) / res)), int(math.floor((y - origin[1]) / res)))
-        if not (0 <= uv[0] < cells.shape[0] and 0 <= uv[1] < cells.shape[1]):
-            raise ValueError(f"{what}: {name} {xy!r} is cell {uv}, outside the map {list(cells.shape)}")
-        ends.append(uv)
+    ends = [map_cell(cells.shape, origin, res, xy, name, what)
+            for name, xy in (("start_xy", start_xy), ("goal_xy", goal_xy))]
     passable = cells == MAP_FREE
     if allow_unknown:
         passable = passable | (cells == MAP_UNKNOWN)

@@ -432,6 +432,19 @@ class ESDF:
             cells.append(cell)
         return cells, snap / self.voxel, max_cost
 
+    def _no_route(self, start_cell, goal_cell, sweeps):
+        """`plan`'s dict in its unreachable shape."""
+        return {"reachable": False, "cells": torch.zeros((0, 3), dtype=torch.int32, device=self.device),
+                "points": torch.zeros((0, 3), dtype=torch.float64, device=self.device), "length_m": math.inf,
+                "min_clearance_m": math.nan, "start_cell": start_cell, "goal_cell": goal_cell, "sweeps": sweeps}
+
+    def _route(self, cells):
+        """(points float64 [L,3], the world coordinates of the lattice `cells` [L,3]; the smallest `dist` over them, a
+        0-d tensor): both stay on the device."""
+        idx = cells.long()
+        lo = torch.tensor(self.lo, dtype=torch.float64, device=self.device)
+        return lo[None, :] + cells.double() * self.voxel, self.dist[idx[:, 0], idx[:, 1], idx[:, 2]].min()
+
     @torch.no_grad()
     def plan(self, start, goal, robot_radius=0.0, allow_unknown=False, snap=0.0, max_cost_m=None):
         """The shortest collision-free route of a robot of `robot_radius` from the world point `start` to `goal` over
@@ -446,10 +459,7 @@ class ESDF:
         (s, g), snap_cells, max_cost = self.plan_arguments([start, goal], robot_radius, snap, max_cost_m)
         passable = self.passable(robot_radius, allow_unknown)
         s, g = _plan.snap_cell(passable, s, snap_cells), _plan.snap_cell(passable, g, snap_cells)
-        dev = self.device
-        out = {"reachable": False, "cells": torch.zeros((0, 3), dtype=torch.int32, device=dev),
-               "points": torch.zeros((0, 3), dtype=torch.float64, device=dev), "length_m": math.inf,
-               "min_clearance_m": math.nan, "start_cell": s, "goal_cell": g, "sweeps": 0}
+        out = self._no_route(s, g, 0)
         if s is None or g is None:
             return out
         field = _plan.geodesic_field(passable, [g], max_cost)
@@ -457,12 +467,10 @@ class ESDF:
         out["sweeps"] = field.sweeps
         if int(cells.shape[0]) == 0:
             return out
-        idx = cells.long()
-        lo = torch.tensor(self.lo, dtype=torch.float64, device=dev)
-        scalars = torch.stack([field.cost[s[0], s[1], s[2]].double(),
-                               self.dist[idx[:, 0], idx[:, 1], idx[:, 2]].min().double()]).cpu().tolist()     # one read
-        out.update(reachable=True, cells=cells, points=lo[None, :] + cells.double() * self.voxel,
-                   length_m=scalars[0] * self.voxel / 1000.0, min_clearance_m=scalars[1])
+        points, clearance = self._route(cells)
+        scalars = torch.stack([field.cost[s[0], s[1], s[2]].double(), clearance.double()]).cpu().tolist()   # one read
+        out.update(reachable=True, cells=cells, points=points, length_m=scalars[0] * self.voxel / 1000.0,
+                   min_clearance_m=scalars[1])
         return out
 
     @torch.no_grad()
@@ -523,12 +531,8 @@ class ESDF:
             raise ValueError(f"ESDF.explore: order must be one of {_frontier.ORDERS} (got {order!r})")
         self.plan_arguments([start], robot_radius, snap, max_cost_m, "ESDF.explore")      # a start is needed here
         fc = self.frontiers(robot_radius, start, snap, max_cost_m, min_cells)
-        dev = self.device
-        out = {"reachable": False, "cells": torch.zeros((0, 3), dtype=torch.int32, device=dev),
-               "points": torch.zeros((0, 3), dtype=torch.float64, device=dev), "length_m": math.inf,
-               "min_clearance_m": math.nan, "start_cell": fc.start_cell, "goal_cell": None,
-               "sweeps": 0 if fc.field is None else fc.field.sweeps, "cluster": None, "n_clusters": fc.n_clusters,
-               "n_kept": 0, "n_reachable": 0, "clusters": fc}
+        out = dict(self._no_route(fc.start_cell, None, 0 if fc.field is None else fc.field.sweeps), cluster=None,
+                   n_clusters=fc.n_clusters, n_kept=0, n_reachable=0, clusters=fc)
         if fc.n_clusters == 0:
             return out
         cols = torch.stack([fc.best_cost.long(), fc.faces.long(), fc.root.long(), fc.keep.long(),
@@ -544,11 +548,9 @@ class ESDF:
         cells = torch.flip(fc.field.path(goal), dims=[0]).contiguous()
         if int(cells.shape[0]) == 0:
             return out
-        idx = cells.long()
-        lo = torch.tensor(self.lo, dtype=torch.float64, device=dev)
-        clearance = float(self.dist[idx[:, 0], idx[:, 1], idx[:, 2]].min().item())
-        out.update(reachable=True, cells=cells, points=lo[None, :] + cells.double() * self.voxel,
-                   length_m=best_cost[row] * self.voxel / 1000.0, min_clearance_m=clearance, goal_cell=goal, cluster=row)
+        points, clearance = self._route(cells)
+        out.update(reachable=True, cells=cells, points=points, length_m=best_cost[row] * self.voxel / 1000.0,
+                   min_clearance_m=float(clearance.item()), goal_cell=goal, cluster=row)
         return out
 
     def save_map(self, directory, up_axis, height, robot_radius=0.0, known_fraction=0.5):

@@ -426,10 +426,11 @@ int gs_esdf_slice(const unsigned char* state, const int* d2, const float* dist, 
  * gs_geodesic_init: seeds i32 [m,3], m >= 0 (NULL allowed for m == 0).  cost = GS_GEO_INF everywhere, then 0 at every
  *   seed that is inside the lattice and passable (others are ignored, duplicates are harmless); both flag buffers
  *   cleared, then the bricks that hold such a seed marked in buffer 0.
- * gs_geodesic_relax: sweeps sweep0 .. sweep0 + k - 1, k >= 1, sweep0 >= 0 the number of sweeps enqueued on this field
- *   so far (it selects the flag buffer: sweep s reads buffer s & 1 and writes the other).  changed u32 [k]: entry s is
- *   non-zero iff sweep sweep0 + s lowered any cell.  One zero entry proves the fixed point; sweeps after it do nothing.
- *   The number of sweeps a field needs may differ between runs; the field does not.
+ * gs_geodesic_relax, and gs_frontier_relax below on its labels: sweeps sweep0 .. sweep0 + k - 1, k >= 1, sweep0 >= 0
+ *   the number of sweeps enqueued on this field so far (it selects the flag buffer: sweep s reads buffer s & 1 and
+ *   writes the other).  changed u32 [k]: entry s is non-zero iff sweep sweep0 + s lowered any cell.  One zero entry
+ *   proves the fixed point; sweeps after it do nothing.  The number of sweeps a field needs may differ between runs;
+ *   the field does not.
  * gs_geodesic_path: start i32[3] by value, max_len >= 1, out_cells i32 [max_len,3], out_n i32 [1].  out_n = 0 when
  *   start lies outside the lattice or holds GS_GEO_INF.  Otherwise out_cells[0] = start, and each step goes to the allowed
  *   neighbour with the smallest cost[n] + w among those with cost[n] < GS_GEO_INF, ties to the lowest move index (at the
@@ -481,10 +482,7 @@ int gs_geodesic_path(const int* cost, const unsigned char* passable, int n0, int
  * gs_frontier_mark: frontier u8 (0 / 1) and label (own index / -1), every element written; counts u32 [4] = the number
  *   of unknown, free, solid and frontier cells; both flag buffers cleared, then the bricks that hold a frontier cell
  *   marked in buffer 0.
- * gs_frontier_relax: sweeps sweep0 .. sweep0 + k - 1, k >= 1, sweep0 >= 0 the number of sweeps enqueued on these labels
- *   so far (sweep s reads flag buffer s & 1 and writes the other).  changed u32 [k]: entry s is non-zero iff sweep
- *   sweep0 + s lowered any label.  One zero entry proves the fixed point; sweeps after it do nothing.  The number of
- *   sweeps may differ between runs; the labels do not.
+ * gs_frontier_relax: sweep0, k, the flag buffers and changed as for gs_geodesic_relax, with "label" for "cell".
  * gs_frontier_roots: counts the roots (label == own index) per block of cells and scans the counts into the workspace
  *   (gs_frontier_workspace_bytes; 0 for sizes outside [1, 1024]); n_roots i32 [1] = K, which the caller reads to size the
  *   table.
