@@ -37,6 +37,7 @@ import torch
 from . import _lib
 from . import frontier as _frontier
 from . import plan as _plan
+from . import view as _view
 from .lietorch_shim import SE3
 from .neus.mesh import Mesh, marching_cubes
 from .pointcloud import _host_index, _rows, ply_colors
@@ -553,6 +554,32 @@ class ESDF:
                    min_clearance_m=float(clearance.item()), goal_cell=goal, cluster=row)
         return out
 
+    def view_candidates(self, start, up_axis, height, robot_radius=0.0, stride=4, snap=0.0, max_cost_m=None,
+                        max_candidates=4096):
+        """Where a robot of `robot_radius` could stand to look around: (cells int32 [V,3], cost int32 [V] in milli-voxels,
+        the GeodesicField), on the device.  A candidate is a passable cell with a route from the world point `start`
+        (placed as `plan` places its endpoints) of at most `max_cost_m`, on a layer of `up_axis` inside `height` (h0, h1)
+        metres by `slice_arguments`' rule, whose two other coordinates are multiples of `stride`; they come by ascending
+        (cost, linear index), the first `max_candidates` of them.  torch ops and one `plan.geodesic_field`; no candidates
+        and a field of None when the start has no passable cell.  ValueError before the device is touched."""
+        return _view.esdf_view_candidates(self, start, up_axis, height, robot_radius, stride, snap, max_cost_m,
+                                          max_candidates)
+
+    def next_view(self, start, camera, up_axis, height, n_yaw=8, robot_radius=0.0, stride=4, snap=0.0, max_cost_m=None,
+                  max_candidates=4096, max_unknown=0, min_gain_cells=1, min_solid_cells=0, lam=0.0):
+        """Where to stand, which way to look and how much of the unknown would be seen from there: the `view_candidates`,
+        each looked from at the `n_yaw` headings 2 pi j / n_yaw about `up_axis` with `camera` = {hfov_deg, vfov_deg, n_u,
+        n_v, range_m, pitch_deg} (view.ray_directions; range_m / voxel rounded down to cells) -- one gs_view_gain call per
+        heading, each with its own tight box (view.view_gain) -- then one read of the [V, n_yaw, 4] table and the costs
+        and the choice on the host (view.choose): among the (view, heading) pairs with unknown >= `min_gain_cells` and
+        solid >= `min_solid_cells` the largest unknown * voxel^3 * exp(-lam * cost_m) wins, equal scores going to the
+        lower cost, then the lower linear index, then the lower heading.  -> `plan`'s dict, the route start to view, plus
+        "view_cell", "view_point", "yaw", "yaw_index", "gain_cells", "gain_m3", "free_cells", "solid_cells", "score",
+        "n_candidates", "n_qualified" and "gains" (the device table); when nothing qualifies, `plan`'s unreachable shape
+        with "view_cell" None.  ValueError before the device is touched."""
+        return _view.esdf_next_view(self, start, camera, up_axis, height, n_yaw, robot_radius, stride, snap, max_cost_m,
+                                    max_candidates, max_unknown, min_gain_cells, min_solid_cells, lam)
+
     def save_map(self, directory, up_axis, height, robot_radius=0.0, known_fraction=0.5):
         """`occupancy_slice` written as `directory`/occupancy.pgm and occupancy.yaml (save_map); returns the slice."""
         grid = self.occupancy_slice(up_axis, height, robot_radius, known_fraction)
@@ -844,8 +871,12 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
     default; start is a world point or "last", the default) the frontier clusters of ESDF.frontiers into
     {output}/map/frontiers.txt (frontier.frontiers_text) and, when ESDF.explore finds a goal, its route into
     {output}/map/explore_path.txt (plan.path_text; `tsdf_frontier_cells`, `tsdf_frontier_clusters`,
-    `tsdf_unknown_fraction` and `tsdf_explore_reachable` in `stats`).  Returns the Mesh, or None when the key is absent or
-    disabled."""
+    `tsdf_unknown_fraction` and `tsdf_explore_reachable` in `stats`), and with next_view = {enable, camera, up_axis,
+    height, n_yaw, robot_radius, stride, snap, start, lam, min_gain_cells, min_solid_cells, max_unknown} (absent by
+    default; start is a world point or "last", the default) the pose of ESDF.next_view into {output}/map/next_view.txt
+    (view.next_view_text) and, when a view is found, its route into {output}/map/next_view_path.txt (plan.path_text;
+    `tsdf_next_view_found`, `tsdf_next_view_gain_m3` and `tsdf_next_view_candidates` in `stats`).  Returns the Mesh, or
+    None when the key is absent or disabled."""
     opt = slam.cfg.get("tsdf") or {}
     if not opt.get("enable", False):
         return None
@@ -925,6 +956,31 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
             print(f"TSDF frontiers: {report['n_frontier']} cells in {report['n_clusters']} clusters, {report['n_kept']} "
                   f"kept, {report['n_reachable']} reachable, unknown_fraction {report['unknown_fraction']!r}, "
                   f"chosen {report['cluster']!r}")
+        nv = ed.get("next_view") or {}
+        if nv.get("enable", False):
+            start = nv.get("start", "last")
+            if isinstance(start, str):
+                if start != "last":
+                    raise ValueError(f"fuse_from_config: tsdf.esdf.next_view.start is a world point or 'last' (got {start!r})")
+                if len(c2w_list) == 0:
+                    raise ValueError("fuse_from_config: tsdf.esdf.next_view needs a camera pose for 'last'")
+                start = torch.as_tensor(c2w_list[-1])[:3, 3]
+            res = field.next_view(start, nv["camera"], nv["up_axis"], nv["height"], n_yaw=nv.get("n_yaw", 8),
+                                  robot_radius=nv.get("robot_radius", 0.0), stride=nv.get("stride", 4),
+                                  snap=nv.get("snap", 0.0), max_unknown=nv.get("max_unknown", 0),
+                                  min_gain_cells=nv.get("min_gain_cells", 1),
+                                  min_solid_cells=nv.get("min_solid_cells", 0), lam=nv.get("lam", 0.0))
+            os.makedirs(f"{slam.output}/map", exist_ok=True)
+            with open(f"{slam.output}/map/next_view.txt", "w") as fh:
+                fh.write(_view.next_view_text(res))
+            if res["view_cell"] is not None:
+                with open(f"{slam.output}/map/next_view_path.txt", "w") as fh:
+                    fh.write(_plan.path_text(res))
+            if stats is not None:
+                stats.update(tsdf_next_view_found=res["view_cell"] is not None, tsdf_next_view_gain_m3=res["gain_m3"],
+                             tsdf_next_view_candidates=res["n_candidates"])
+            print(f"TSDF next view: cell {res['view_cell']!r}, yaw {res['yaw']!r}, gain_m3 {res['gain_m3']!r}, "
+                  f"{res['n_candidates']} candidates, {res['n_qualified']} qualified")
     meshing = slam.cfg.get("meshing") or {}
     gt_path = meshing.get("gt_mesh_path") or ""
     if meshing.get("eval_rec") and gt_path.find(".ply") > -1 and os.path.exists(gt_path) and len(mesh.faces) > 0:

@@ -503,6 +503,37 @@ int gs_frontier_table(const unsigned char* state, const int* label, const int* c
                       const void* workspace, size_t workspace_bytes, int rows, int capacity, int* root, int* size,
                       int* faces, long long* sum, int* bbox, int* best, gs_stream_t stream);
 
+/* ---- View gain: the cells of a state lattice that a camera's rays cross from a candidate pose (no counterpart in the
+ *      reference), csrc/view_gain.hip; tests/view_gain_restatement.py restates it serially ----
+ *
+ * The lattice and state are those of the frontier block above (each size in [1, 1024]; 0 unknown, 1 free, any other value
+ * solid).  origins i32 [V,3] in cells, V >= 0 (V == 0 launches nothing).  dirs i32 [R,3], 1 <= R <= 65536, the same rays
+ * for every view of the call, every component in [-GS_VIEW_MAX_DIR, GS_VIEW_MAX_DIR]; an all-zero direction casts nothing
+ * (nor does one with a component outside that range: the caller's mistake, made harmless).  range2 in [1, 3 * 1023^2], the
+ * squared range in cells.  max_unknown >= 0, 0 for no limit.  box: six HOST ints lo0, lo1, lo2, hi0, hi1, hi2, offsets
+ * from a view's origin with lo <= 0 <= hi on every axis and at most GS_VIEW_MAX_BOX_CELLS cells prod(hi - lo + 1).
+ * Everything is integer.  Bad sizes, ranges, NULL where a pointer is needed or such a box return GS_ERR_INVALID_ARG
+ * before anything is launched or written; the call enqueues on the stream and reads nothing back.
+ *
+ * The walk of one ray, origin o, direction d, s_a = sign(d_a), w_a = |d_a|, one step counter k_a per axis from 0:
+ *   the ray visits o first.  The next cell lies one step along s_a on the axis a with w_a != 0 that minimises the time
+ *   (2 k_a + 1) / (2 w_a) at which a ray from the cell's centre crosses into it, compared exactly: a beats b when
+ *   (2 k_a + 1) * w_b < (2 k_b + 1) * w_a, a tie goes to the lower axis (both products stay below 2^31).  The ray ends,
+ *   without visiting that cell, when it lies outside the lattice, outside o + [lo, hi], or at a squared distance from o
+ *   above range2; else k_a goes up by one and the cell is visited.  After visiting a solid cell the ray ends.  After
+ *   visiting its max_unknown-th unknown cell (counted per ray, over every unknown cell it crosses) it ends, when
+ *   max_unknown > 0.  The offsets never shrink, so a ray takes at most floor(sqrt(3 * range2)) steps.
+ * A view whose origin lies outside the lattice casts nothing.
+ * gain u32 [V,4]: per view the number of distinct unknown, free and solid cells visited by any of its rays, and their
+ *   sum, the distinct cells in all.  A set has no order: the counts do not depend on the order of rays or lanes.
+ * gs_view_gain_lds_bytes: the dynamic LDS one workgroup (one view) takes for this box, one bit per cell plus the
+ *   reduction's words; 0 for a box the call refuses.                                                                  */
+#define GS_VIEW_MAX_BOX_CELLS 1048576        /* one bit per cell: 128 KiB of the CU's 160 KiB of LDS */
+#define GS_VIEW_MAX_DIR 32767
+size_t gs_view_gain_lds_bytes(const int* box);
+int gs_view_gain(const unsigned char* state, int n0, int n1, int n2, const int* origins, int n_views, const int* dirs,
+                 int n_rays, int range2, int max_unknown, const int* box, unsigned int* gain, gs_stream_t stream);
+
 /* ---- frame preprocessing of the dataset readers (src/datasets.py:96-143, 565-605), csrc/frame_prep.hip ----
  *
  * Semantics: tests/frame_prep_restatement.py, bit for bit (cv2.remap / cv2.resize INTER_LINEAR on 8-bit data,
