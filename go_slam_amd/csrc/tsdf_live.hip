@@ -3,13 +3,9 @@
 // Contract: include/goslam_hip.h (gs_tsdf_accumulate, gs_tsdf_resolve, gs_tsdf_frame_change);
 // tests/tsdf_live_restatement.py restates the three serially.
 //
-// tsdf_accumulate_kernel has tsdf_integrate_kernel's shape: one lane per lattice point, the 64 lanes of a wave along z,
-// four waves per workgroup on consecutive runs, up to GS_TSDF_BATCH frames per launch with the point's state (two i32,
-// with images six) loaded once, carried in registers over the batch and stored once.  A frame's matrix and its sign sit
-// at wave-uniform addresses and are read by scalar loads.  The geometry up to s = fminf(1, sdf / trunc) is that kernel's
-// operation for operation, the per-run frustum test (tsdf_common.h) included.  What follows is integer: the observation
-// is quantised once and added with the frame's sign, so the state is a sum over frames that commutes and has an exact
-// inverse.  No LDS, no atomics: every point is owned by one lane.
+// tsdf_accumulate_kernel is the sweep of tsdf_common.h (tsdf_fuse), the one tsdf_integrate_kernel is, with SumRule: a
+// point's state is two i32, with images six.  An observation is quantised once and added with its frame's sign (at a
+// wave-uniform address: a scalar load), so the state is a sum over frames that commutes and has an exact inverse.
 //
 // tsdf_resolve_kernel: one lane per point, the state turned into the fp32 lattices TSDFVolume's consumers read.
 // tsdf_frame_change_kernel: one workgroup per frame, fp64 partial sums over the pixels a lane strides over, a butterfly
@@ -19,79 +15,51 @@
 
 namespace {
 
-template <bool COLOR>
-__global__ __launch_bounds__(TSDF_THREADS) void tsdf_accumulate_kernel(
-    int* __restrict__ sum_s, int* __restrict__ count, int* __restrict__ sum_rgb, int* __restrict__ count_rgb,
-    const float* __restrict__ depth, const float* __restrict__ mask, const float* __restrict__ images,
-    const float* __restrict__ w2c, const int* __restrict__ sign, int nframes, TsdfCam cam, float lox, float loy,
-    float loz, float voxel, float trunc, int ny, int nz, int zchunks, long long nruns, long long npoints) {
-  // the wave's run: wave-uniform, so everything derived from it lives in SGPRs and the frame branches are scalar
-  const long long run = (long long)blockIdx.x * TSDF_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (run >= nruns) return;
-  const int lane = threadIdx.x & 63;
-  const long long row = run / zchunks;
-  const int zc = (int)(run - row * zchunks);
-  const int i = (int)(row / ny), j = (int)(row - (long long)i * ny);
-  const float px = lox + (float)i * voxel;
-  const float py = loy + (float)j * voxel;
+struct SumRule {
+  int* sum_s;
+  int* count;
+  int* sum_rgb;            // planar [3,npoints], and count_rgb: touched only by the COLOR kernel
+  int* count_rgb;
+  const int* sign;         // [nframes] of the batch, +1 or -1
+  struct State { int ss, cn, sr, sg, sb, cc; };
 
-  // bit f set: frame f may touch this run (its 64 points, whether or not the lattice ends inside it)
-  const float pz0 = loz + (float)(zc * 64) * voxel, pz1 = loz + (float)(zc * 64 + 63) * voxel;
-  unsigned live = 0;
-  for (int f = 0; f < nframes; ++f)
-    if (tsdf_run_may_hit(w2c + f * 12, cam, px, py, pz0, pz1, voxel)) live |= 1u << f;
-  if (live == 0) return;
-
-  const int k = zc * 64 + lane;
-  if (k >= nz) return;
-  const float pz = loz + (float)k * voxel;
-  const size_t at = (size_t)row * nz + k;
-  const size_t hw = (size_t)cam.h * cam.w;
-  int ss = sum_s[at], cn = count[at];
-  int sr = 0, sg = 0, sb = 0, cc = 0;
-  if (COLOR) {
-    sr = sum_rgb[at];
-    sg = sum_rgb[(size_t)npoints + at];
-    sb = sum_rgb[(size_t)2 * npoints + at];
-    cc = count_rgb[at];
-  }
-  for (int f = 0; f < nframes; ++f) {
-    if (!((live >> f) & 1u)) continue;
-    const float* __restrict__ m = w2c + f * 12;
-    const float z = ((m[8] * px + m[9] * py) + m[10] * pz) + m[11];
-    if (!(z > 1e-3f)) continue;
-    const float x = ((m[0] * px + m[1] * py) + m[2] * pz) + m[3];
-    const float y = ((m[4] * px + m[5] * py) + m[6] * pz) + m[7];
-    const float u = cam.fx * (x / z) + cam.cx;
-    const float v = cam.fy * (y / z) + cam.cy;
-    const float fu = floorf(u + 0.5f), fv = floorf(v + 0.5f);
-    if (!(fu >= 0.0f && fu < (float)cam.w && fv >= 0.0f && fv < (float)cam.h)) continue;
-    const size_t pix = (size_t)f * hw + (size_t)((int)fv * cam.w + (int)fu);
-    const float d = depth[pix];
-    if (!(d > 0.0f)) continue;
-    if (mask && mask[pix] == 0.0f) continue;
-    const float sdf = d - z;
-    if (sdf < -trunc) continue;
-    const float s = fminf(1.0f, sdf / trunc);
-    const int sn = sign[f];
-    ss += sn * (int)rintf(s * 16384.0f);
-    cn += sn;
-    if (COLOR && sdf <= trunc) {
-      const float* __restrict__ img = images + (size_t)f * 3 * hw + (pix - (size_t)f * hw);
-      sr += sn * (int)rintf(fminf(fmaxf(img[0], 0.0f), 1.0f) * 255.0f);
-      sg += sn * (int)rintf(fminf(fmaxf(img[hw], 0.0f), 1.0f) * 255.0f);
-      sb += sn * (int)rintf(fminf(fmaxf(img[2 * hw], 0.0f), 1.0f) * 255.0f);
-      cc += sn;
+  __device__ __forceinline__ void load(State& p, size_t at, size_t npoints, bool color) const {
+    p.ss = sum_s[at];
+    p.cn = count[at];
+    p.sr = p.sg = p.sb = p.cc = 0;
+    if (color) {
+      p.sr = sum_rgb[at];
+      p.sg = sum_rgb[npoints + at];
+      p.sb = sum_rgb[2 * npoints + at];
+      p.cc = count_rgb[at];
     }
   }
-  sum_s[at] = ss;
-  count[at] = cn;
-  if (COLOR) {
-    sum_rgb[at] = sr;
-    sum_rgb[(size_t)npoints + at] = sg;
-    sum_rgb[(size_t)2 * npoints + at] = sb;
-    count_rgb[at] = cc;
+  __device__ __forceinline__ void fold(State& p, int f, float s, const float* img, size_t hw) const {
+    const int sn = sign[f];
+    p.ss += sn * (int)rintf(s * 16384.0f);
+    p.cn += sn;
+    if (img) {
+      p.sr += sn * (int)rintf(fminf(fmaxf(img[0], 0.0f), 1.0f) * 255.0f);
+      p.sg += sn * (int)rintf(fminf(fmaxf(img[hw], 0.0f), 1.0f) * 255.0f);
+      p.sb += sn * (int)rintf(fminf(fmaxf(img[2 * hw], 0.0f), 1.0f) * 255.0f);
+      p.cc += sn;
+    }
   }
+  __device__ __forceinline__ void store(const State& p, size_t at, size_t npoints, bool color) const {
+    sum_s[at] = p.ss;
+    count[at] = p.cn;
+    if (color) {
+      sum_rgb[at] = p.sr;
+      sum_rgb[npoints + at] = p.sg;
+      sum_rgb[2 * npoints + at] = p.sb;
+      count_rgb[at] = p.cc;
+    }
+  }
+};
+
+template <bool COLOR>
+__global__ __launch_bounds__(TSDF_THREADS) void tsdf_accumulate_kernel(SumRule rule, TsdfSweep sw) {
+  tsdf_fuse<COLOR>(rule, sw);
 }
 
 template <bool COLOR>
@@ -170,35 +138,13 @@ extern "C" int gs_tsdf_accumulate(int* sum_s, int* count, int* sum_rgb, int* cou
                                   const float* depth, const float* mask, const float* images, const float* w2c,
                                   const int* sign, int k, int h, int w, float fx, float fy, float cx, float cy,
                                   float lo_x, float lo_y, float lo_z, float voxel, float trunc, gs_stream_t stream) {
-  GS_REQUIRE(tsdf_dims_ok(nx, ny, nz), "tsdf_accumulate: lattice %d x %d x %d outside [2, 1024]", nx, ny, nz);
   GS_REQUIRE(sum_s && count && depth && w2c && sign, "tsdf_accumulate: null pointer");
   GS_REQUIRE(!images || (sum_rgb && count_rgb), "tsdf_accumulate: images without the colour sums and their count");
-  GS_REQUIRE(k >= 0 && h > 0 && w > 0 && (long long)h * w <= (1LL << 30), "tsdf_accumulate: k=%d h=%d w=%d", k, h, w);
   GS_REQUIRE(fx > 0.0f && fy > 0.0f && voxel > 0.0f && trunc > 0.0f, "tsdf_accumulate: fx=%g fy=%g voxel=%g trunc=%g",
              fx, fy, voxel, trunc);
-  const TsdfCam cam = tsdf_cam(fx, fy, cx, cy, h, w);
-  const int zchunks = gs_cdiv(nz, 64);
-  const long long nruns = (long long)nx * ny * zchunks;
-  const long long npoints = (long long)nx * ny * nz;
-  const unsigned blocks = (unsigned)((nruns + TSDF_WAVES - 1) / TSDF_WAVES);
-  const size_t hw = (size_t)h * w;
-  for (int f0 = 0; f0 < k; f0 += GS_TSDF_BATCH) {
-    const int nb = (k - f0 < GS_TSDF_BATCH) ? k - f0 : GS_TSDF_BATCH;
-    const float* d = depth + (size_t)f0 * hw;
-    const float* mk = mask ? mask + (size_t)f0 * hw : nullptr;
-    const float* m = w2c + (size_t)f0 * 12;
-    GS_TIMING_PRE();
-    if (images)
-      tsdf_accumulate_kernel<true><<<blocks, TSDF_THREADS, 0, (hipStream_t)stream>>>(
-          sum_s, count, sum_rgb, count_rgb, d, mk, images + (size_t)f0 * 3 * hw, m, sign + f0, nb, cam, lo_x, lo_y, lo_z,
-          voxel, trunc, ny, nz, zchunks, nruns, npoints);
-    else
-      tsdf_accumulate_kernel<false><<<blocks, TSDF_THREADS, 0, (hipStream_t)stream>>>(
-          sum_s, count, nullptr, nullptr, d, mk, nullptr, m, sign + f0, nb, cam, lo_x, lo_y, lo_z, voxel, trunc, ny, nz,
-          zchunks, nruns, npoints);
-    GS_CHECK_LAUNCH("tsdf_accumulate");
-  }
-  return GS_OK;
+  return tsdf_fuse_enqueue("tsdf_accumulate", tsdf_accumulate_kernel<true>, tsdf_accumulate_kernel<false>, nx, ny, nz,
+                           depth, mask, images, w2c, k, h, w, fx, fy, cx, cy, lo_x, lo_y, lo_z, voxel, trunc, stream,
+                           [=](int f0) { return SumRule{sum_s, count, sum_rgb, count_rgb, sign + f0}; });
 }
 
 extern "C" int gs_tsdf_resolve(const int* sum_s, const int* count, const int* sum_rgb, const int* count_rgb, int nx,

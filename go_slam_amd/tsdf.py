@@ -81,6 +81,29 @@ def _intrinsics4(intrinsics, what):
     return [float(v) for v in intr]
 
 
+def fusion_inputs(what, dev, depth, w2c, intrinsics, images=None, mask=None):
+    """The frames `TSDFVolume.integrate` and `ReversibleTSDF.accumulate` take, checked on the host -- depth [K,H,W], K
+    poses, images [K,3,H,W], mask [K,H,W], four intrinsics; ValueError under the caller's name `what` -- and only then
+    moved to `dev` as contiguous float32 -> (K, H, W, depth, [K,3,4] matrices, images, mask, [fx, fy, cx, cy])."""
+    depth = torch.as_tensor(depth)
+    if depth.dim() != 3:
+        raise ValueError(f"{what}: depth must be [K,H,W] (got {list(depth.shape)})")
+    K, H, W = (int(s) for s in depth.shape)
+    w2c = torch.as_tensor(w2c)
+    if w2c.dim() > 0 and w2c.shape[0] != K:
+        raise ValueError(f"{what}: {w2c.shape[0]} poses for {K} depth maps")
+    frames = [depth]
+    for t, name, shape in ((images, "images", (K, 3, H, W)), (mask, "mask", (K, H, W))):
+        t = None if t is None else torch.as_tensor(t)
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"{what}: {name} must be {list(shape)} (got {list(t.shape)})")
+        frames.append(t)
+    intr = _intrinsics4(intrinsics, what)
+    mats = w2c_matrices(w2c).to(dev)
+    depth, images, mask = (None if t is None else t.to(device=dev, dtype=torch.float32).contiguous() for t in frames)
+    return K, H, W, depth, mats, images, mask, intr
+
+
 def lattice(bound, voxel_size, trunc, what):
     """(voxel, lo float64 [3], dims, trunc) of the lattice over `bound` ([3,2]: lo, hi per axis): points at
     lo + idx * voxel, n = ceil((hi - lo) / voxel) + 1 per axis, truncation 4 voxels unless given.  ValueError for a bad
@@ -132,24 +155,8 @@ class TSDFVolume:
         intrinsics (fx, fy, cx, cy) of the depth maps, images [K,3,H,W] in [0,1] and mask [K,H,W] (0 drops a pixel)
         optional.  Enqueues ceil(K / batch) launches on the current stream; nothing is read back."""
         dev = self.device
-
-        def f32(t, what, shape):
-            t = torch.as_tensor(t).to(device=dev, dtype=torch.float32).contiguous()
-            if tuple(t.shape) != shape:
-                raise ValueError(f"TSDFVolume.integrate: {what} must be {list(shape)} (got {list(t.shape)})")
-            return t
-
-        depth = torch.as_tensor(depth)
-        if depth.dim() != 3:
-            raise ValueError(f"TSDFVolume.integrate: depth must be [K,H,W] (got {list(depth.shape)})")
-        K, H, W = (int(s) for s in depth.shape)
-        depth = f32(depth, "depth", (K, H, W))
-        mats = w2c_matrices(w2c).to(dev)
-        if mats.shape[0] != K:
-            raise ValueError(f"TSDFVolume.integrate: {mats.shape[0]} poses for {K} depth maps")
-        images = None if images is None else f32(images, "images", (K, 3, H, W))
-        mask = None if mask is None else f32(mask, "mask", (K, H, W))
-        intr = _intrinsics4(intrinsics, "TSDFVolume.integrate")
+        K, H, W, depth, mats, images, mask, intr = fusion_inputs("TSDFVolume.integrate", dev, depth, w2c, intrinsics,
+                                                                 images, mask)
         if K == 0:
             return self
         nx, ny, nz = self.dims

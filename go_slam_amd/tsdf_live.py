@@ -19,7 +19,7 @@ import torch
 from . import _lib
 from .lietorch_shim import SE3
 from .pointcloud import _rows
-from .tsdf import (CHUNK, TSDFVolume, _intrinsics4, _inverse, _sensor_needs_rgbd, keyframe_observations, lattice,
+from .tsdf import (CHUNK, TSDFVolume, _inverse, _sensor_needs_rgbd, fusion_inputs, keyframe_observations, lattice,
                    w2c_matrices)
 
 MAX_LIVE = 65535           # frames alive in one volume: 16384 * 65535 < 2^30 keeps sum_s inside i32
@@ -74,32 +74,14 @@ class ReversibleTSDF:
         on the current stream; nothing is read back."""
         what = "ReversibleTSDF.accumulate"
         dev = self.device
-
-        def f32(t, name, shape):
-            t = torch.as_tensor(t)
-            if tuple(t.shape) != shape:
-                raise ValueError(f"{what}: {name} must be {list(shape)} (got {list(t.shape)})")
-            return t
-
         depth = torch.as_tensor(depth)
-        if depth.dim() != 3:
-            raise ValueError(f"{what}: depth must be [K,H,W] (got {list(depth.shape)})")
-        K, H, W = (int(s) for s in depth.shape)
-        signs = _signs(sign, K)
+        signs = _signs(sign, depth.shape[0] if depth.dim() else 0)      # a depth that is not [K,H,W] is refused below
         if self.n_live + sum(signs) > MAX_LIVE:
             raise ValueError(f"{what}: {self.n_live} frames alive and {sum(signs)} more exceed {MAX_LIVE}, the number the "
                              "int32 sums are sized for")
-        w2c = torch.as_tensor(w2c)
-        if w2c.shape[0] != K:
-            raise ValueError(f"{what}: {w2c.shape[0]} poses for {K} depth maps")
-        images = None if images is None else f32(images, "images", (K, 3, H, W))
-        mask = None if mask is None else f32(mask, "mask", (K, H, W))
-        intr = _intrinsics4(intrinsics, what)
-        mats = w2c_matrices(w2c).to(dev)
+        K, H, W, depth, mats, images, mask, intr = fusion_inputs(what, dev, depth, w2c, intrinsics, images, mask)
         if K == 0:
             return self
-        depth, images, mask = (None if t is None else t.to(device=dev, dtype=torch.float32).contiguous()
-                               for t in (depth, images, mask))
         sign_d = torch.tensor(signs, dtype=torch.int32).to(dev)
         nx, ny, nz = self.dims
         self._stale = True

@@ -89,6 +89,54 @@ def test_accumulate_is_the_restatement_bit_for_bit(arc_frames, arc_reference):
     assert vol.n_live == 0 and not any(bool(t.any()) for t in vol.state())
 
 
+@pytest.mark.parametrize("images", [True, False])
+def test_both_fusions_count_the_same_observations(arc_frames, arc_reference, images):
+    """The running mean and the integer sums are one sweep with two rules: with no weight cap in reach, a point's weight
+    and its count are the number of frames that update it, the restatement's."""
+    K = len(arc_frames[0])
+    mean = TG.integrate(TG.volume(max_weight=64.0), arc_frames, images=images)
+    rev = accumulate(live_volume(), arc_frames, images=images)
+    want = arc_reference["count"]
+    assert K <= 64 and want.max() > TG.batch() and (want == 0).any()
+    assert np.array_equal(TG.bits(mean.weight), TG.bits(rev.count.float()))
+    assert np.array_equal(TG.bits(mean.weight), TG.bits(want.astype(np.float32)))
+    assert np.array_equal(rev.count.cpu().numpy(), want)
+
+
+SMALL_BOUND = [[0.75, 1.0], [0.5, 0.625], [-2.0, 6.0]]         # 3 x 2 x 65 at VOXEL: a second 64-point run of one point
+
+
+def test_a_lattice_one_point_longer_than_a_run_is_the_restatement(arc_frames):
+    """batch + 1 frames, so a second launch of one frame, on the smallest lattice with a ragged second run and ny = 2:
+    arc frames, which see the first run only, a camera at z = 5.99 that has nothing but the plane k = 64 in front of it,
+    one at z = 4 that sees both runs and one that looks away.  accumulate takes them with mixed signs."""
+    dims, lo = (3, 2, 65), [b[0] for b in SMALL_BOUND]
+    arc = list(range(0, len(arc_frames[0]), 2))[:TG.batch() - 2]
+    parts = [pick(arc_frames, arc[:5]), TG.one_frame(np.eye(3), (0.875, 0.5, 5.99), 0.3), pick(arc_frames, arc[5:10]),
+             TG.one_frame(np.eye(3), (0.875, 0.5625, 4.0), 2.0),
+             TG.one_frame(np.diag([-1.0, 1.0, -1.0]), (0.75, 0.5, -3.0), 2.0), pick(arc_frames, arc[10:])]
+    frames = tuple(np.concatenate([p[i] for p in parts]) for i in range(4))
+    depth, mats, img, mask = frames
+    K = len(depth)
+    assert K == TG.batch() + 1 and not mask.all() and not depth.all()
+    signs = [1, 1, -1, 1, 1, 1, -1, 1, 1, 1, 1, -1, -1, 1, -1, 1, -1]
+    # not vacuous: some points are updated and some are not, the spilled plane is, and one frame updates nothing else
+    ref = TG.restate(frames, dims, lo, VOXEL, TRUNC)
+    touched = ref["weight"] > 0
+    alone = TG.restate(pick(frames, [5]), dims, lo, VOXEL, TRUNC)["weight"] > 0
+    print("points touched:", int(touched.sum()), "of", touched.size, "on k = 64:", int(touched[:, :, 64].sum()))
+    assert 0 < touched.sum() < touched.size and touched[:, :, 64].any() and (ref["colors"] > 0).any()
+    assert alone[:, :, 64].any() and not alone[:, :, :64].any()
+    vol = TG.integrate(TG.volume(SMALL_BOUND), frames)
+    assert vol.dims == dims
+    TG.assert_state(vol, ref)
+    state = LR.accumulate(LR.new_state(dims), depth, mats, INTR, lo, VOXEL, TRUNC, images=img, mask=mask, sign=signs)
+    assert len(set(signs[:TG.batch()])) == 2 and state["count"].min() < 0 < state["count"].max()
+    rev = accumulate(live_volume(SMALL_BOUND), frames, sign=signs)
+    assert rev.dims == dims and rev.n_live == sum(signs)
+    assert_state(rev, state)
+
+
 def test_frames_taken_out_leave_a_fresh_fusion_of_the_rest(arc_frames, arc_reference):
     K = len(arc_frames[0])
     rest = [f for f in range(K) if f not in OUT]

@@ -1,8 +1,8 @@
 """csrc/tsdf_live.hip restated in NumPy, straight from include/goslam_hip.h (gs_tsdf_accumulate, gs_tsdf_resolve,
 gs_tsdf_frame_change): serial over frames, vectorised over lattice points, fp32 with one rounding per operation.
 
-accumulate, per lattice point and frame: gs_tsdf_integrate's geometry (the sequence tsdf_restatement.integrate walks, the
-same operations in the same order) up to s = fminf(1, sdf / trunc), then in int32
+accumulate, per lattice point and frame: gs_tsdf_integrate's geometry (tsdf_restatement.frame_geometry, the function
+tsdf_restatement.integrate walks) and s = fminf(1, sdf / trunc), then in int32
 
     q = (int)rintf(s * 16384.0f) ; sum_s += sign * q ; count += sign
     if images and sdf <= trunc: c = (int)rintf(fminf(fmaxf(img, 0), 1) * 255.0f) per channel ; sum_rgb += sign * c ;
@@ -16,6 +16,8 @@ a wave's butterfly v += v[lane ^ m], m = 32 .. 1; the four waves as ((w0 + w1) +
 """
 import numpy as np
 
+from tsdf_restatement import frame_geometry, lattice_axes
+
 Q = 16384.0
 
 
@@ -25,49 +27,13 @@ def new_state(dims, color=True):
             "count_rgb": z(*dims) if color else None}
 
 
-def _frame(f, depth, w2c, intr, px, py, pz, trunc, mask):
-    """The geometry of one frame: (sel flat indices of the points that are updated, sdf, iu, iv), float32."""
-    T = np.float32
-    fx, fy, cx, cy = (T(v) for v in intr)
-    tr, half, near = T(trunc), T(0.5), T(1e-3)
-    _, H, W = depth.shape
-    m = np.asarray(w2c[f]).astype(T)
-    z = (((m[2, 0] * px + m[2, 1] * py) + m[2, 2] * pz) + m[2, 3]).reshape(-1)
-    x = (((m[0, 0] * px + m[0, 1] * py) + m[0, 2] * pz) + m[0, 3]).reshape(-1)
-    y = (((m[1, 0] * px + m[1, 1] * py) + m[1, 2] * pz) + m[1, 3]).reshape(-1)
-    sel = np.nonzero(z > near)[0]
-    x, y, z = x[sel], y[sel], z[sel]
-    u = fx * (x / z) + cx
-    v = fy * (y / z) + cy
-    fu, fv = np.floor(u + half), np.floor(v + half)
-    ok = (fu >= 0) & (fu < T(W)) & (fv >= 0) & (fv < T(H))
-    sel, z = sel[ok], z[ok]
-    iu, iv = fu[ok].astype(np.int64), fv[ok].astype(np.int64)
-    d = depth[f, iv, iu]
-    ok = d > 0
-    if mask is not None:
-        ok &= ~(np.asarray(mask[f]).astype(T)[iv, iu] == 0)
-    sel, z, d, iu, iv = sel[ok], z[ok], d[ok], iu[ok], iv[ok]
-    sdf = d - z
-    ok = ~(sdf < -tr)
-    return sel[ok], sdf[ok], iu[ok], iv[ok]
-
-
-def _lattice_axes(dims, lo, voxel):
-    T = np.float32
-    nx, ny, nz = dims
-    vx = T(voxel)
-    return ((T(lo[0]) + np.arange(nx).astype(T) * vx)[:, None, None], (T(lo[1]) + np.arange(ny).astype(T) * vx)[None, :, None],
-            (T(lo[2]) + np.arange(nz).astype(T) * vx)[None, None, :])
-
-
 def accumulate(state, depth, w2c, intr, lo, voxel, trunc, images=None, mask=None, sign=1, observations=None):
     """In place on `state` (new_state's dict).  depth [K,H,W], w2c [K,3,4], images [K,3,H,W] or None, mask [K,H,W] or
     None, sign a scalar or [K] integers.  With a list `observations`, appends per frame (sel, s float32, colour sel,
     clamped colours float32 [3,n]) -- the values before quantisation."""
     T = np.float32
     dims = state["sum_s"].shape
-    px, py, pz = _lattice_axes(dims, lo, voxel)
+    px, py, pz = lattice_axes(dims, lo, voxel)
     depth = np.asarray(depth).astype(T)
     K = depth.shape[0]
     signs = np.broadcast_to(np.asarray(sign, np.int32), (K,))
@@ -76,7 +42,7 @@ def accumulate(state, depth, w2c, intr, lo, voxel, trunc, images=None, mask=None
     tr, one = T(trunc), T(1.0)
     with np.errstate(all="ignore"):
         for f in range(K):
-            sel, sdf, iu, iv = _frame(f, depth, w2c, intr, px, py, pz, trunc, mask)
+            sel, sdf, iu, iv = frame_geometry(f, depth, w2c, intr, px, py, pz, trunc, mask)
             s = np.fmin(one, sdf / tr)
             q = np.rint(s * T(Q)).astype(np.int32)
             sum_s[sel] += signs[f] * q

@@ -31,43 +31,58 @@ def lattice_dims(bound, voxel):
     return tuple(int(np.ceil((bound[a, 1] - bound[a, 0]) / voxel)) + 1 for a in range(3))
 
 
+def lattice_axes(dims, lo, voxel, dtype=np.float32):
+    """(px [nx,1,1], py [1,ny,1], pz [1,1,nz]): lo + float(idx) * voxel per axis, in `dtype`."""
+    T = dtype
+    nx, ny, nz = dims
+    vx = T(voxel)
+    return ((T(lo[0]) + np.arange(nx).astype(T) * vx)[:, None, None], (T(lo[1]) + np.arange(ny).astype(T) * vx)[None, :, None],
+            (T(lo[2]) + np.arange(nz).astype(T) * vx)[None, None, :])
+
+
+def frame_geometry(f, depth, w2c, intr, px, py, pz, trunc, mask, dtype=np.float32):
+    """The contract's steps up to the sdf < -trunc skip for frame f of depth ([K,H,W], already in `dtype`): (sel flat
+    indices of the lattice points that are updated, sdf, iu, iv).  tsdf_live_restatement.accumulate walks it too."""
+    T = dtype
+    fx, fy, cx, cy = (T(v) for v in intr)
+    tr, half, near = T(trunc), T(0.5), T(1e-3)
+    _, H, W = depth.shape
+    m = np.asarray(w2c[f]).astype(T)
+    z = (((m[2, 0] * px + m[2, 1] * py) + m[2, 2] * pz) + m[2, 3]).reshape(-1)
+    x = (((m[0, 0] * px + m[0, 1] * py) + m[0, 2] * pz) + m[0, 3]).reshape(-1)
+    y = (((m[1, 0] * px + m[1, 1] * py) + m[1, 2] * pz) + m[1, 3]).reshape(-1)
+    sel = np.nonzero(z > near)[0]
+    x, y, z = x[sel], y[sel], z[sel]
+    u = fx * (x / z) + cx
+    v = fy * (y / z) + cy
+    fu, fv = np.floor(u + half), np.floor(v + half)
+    ok = (fu >= 0) & (fu < T(W)) & (fv >= 0) & (fv < T(H))
+    sel, z = sel[ok], z[ok]
+    iu, iv = fu[ok].astype(np.int64), fv[ok].astype(np.int64)
+    d = depth[f, iv, iu]
+    ok = d > 0
+    if mask is not None:
+        ok &= ~(np.asarray(mask[f]).astype(T)[iv, iu] == 0)
+    sel, z, d, iu, iv = sel[ok], z[ok], d[ok], iu[ok], iv[ok]
+    sdf = d - z
+    ok = ~(sdf < -tr)
+    return sel[ok], sdf[ok], iu[ok], iv[ok]
+
+
 def integrate(vol, depth, w2c, intr, lo, voxel, trunc, max_weight=64.0, images=None, mask=None, dtype=np.float32):
     """In place on vol (new_volume's dict).  depth [K,H,W], w2c [K,3,4], images [K,3,H,W] or None, mask [K,H,W] or None;
     every input is first rounded to `dtype`."""
     T = dtype
-    nx, ny, nz = vol["tsdf"].shape
-    fx, fy, cx, cy = (T(v) for v in intr)
-    vx, tr, mw, one, half, near = T(voxel), T(trunc), T(max_weight), T(1.0), T(0.5), T(1e-3)
-    px = (T(lo[0]) + np.arange(nx).astype(T) * vx)[:, None, None]
-    py = (T(lo[1]) + np.arange(ny).astype(T) * vx)[None, :, None]
-    pz = (T(lo[2]) + np.arange(nz).astype(T) * vx)[None, None, :]
+    tr, mw, one = T(trunc), T(max_weight), T(1.0)
+    px, py, pz = lattice_axes(vol["tsdf"].shape, lo, voxel, T)
     depth = np.asarray(depth).astype(T)
-    K, H, W = depth.shape
+    K = depth.shape[0]
     tsdf, weight = vol["tsdf"].reshape(-1), vol["weight"].reshape(-1)
     colors = vol["colors"].reshape(3, -1)
     assert tsdf.dtype == T and np.shares_memory(tsdf, vol["tsdf"])
     with np.errstate(all="ignore"):
         for f in range(K):
-            m = np.asarray(w2c[f]).astype(T)
-            z = (((m[2, 0] * px + m[2, 1] * py) + m[2, 2] * pz) + m[2, 3]).reshape(-1)
-            x = (((m[0, 0] * px + m[0, 1] * py) + m[0, 2] * pz) + m[0, 3]).reshape(-1)
-            y = (((m[1, 0] * px + m[1, 1] * py) + m[1, 2] * pz) + m[1, 3]).reshape(-1)
-            sel = np.nonzero(z > near)[0]
-            x, y, z = x[sel], y[sel], z[sel]
-            u = fx * (x / z) + cx
-            v = fy * (y / z) + cy
-            fu, fv = np.floor(u + half), np.floor(v + half)
-            ok = (fu >= 0) & (fu < T(W)) & (fv >= 0) & (fv < T(H))
-            sel, z = sel[ok], z[ok]
-            iu, iv = fu[ok].astype(np.int64), fv[ok].astype(np.int64)
-            d = depth[f, iv, iu]
-            ok = d > 0
-            if mask is not None:
-                ok &= ~(np.asarray(mask[f]).astype(T)[iv, iu] == 0)
-            sel, z, d, iu, iv = sel[ok], z[ok], d[ok], iu[ok], iv[ok]
-            sdf = d - z
-            ok = ~(sdf < -tr)
-            sel, sdf, iu, iv = sel[ok], sdf[ok], iu[ok], iv[ok]
+            sel, sdf, iu, iv = frame_geometry(f, depth, w2c, intr, px, py, pz, trunc, mask, T)
             s = np.minimum(one, sdf / tr)
             w0 = weight[sel]
             w1 = w0 + one

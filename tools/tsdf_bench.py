@@ -42,7 +42,7 @@ def make_volume(n, scene):
         voxel, lo = 8.0 / n, (-4.0, -4.0, -2.0)
     else:
         voxel, lo = 1.0 / n, (-0.4, -0.6, 3.4)
-    bound = [[l, l + (n - 1) * voxel] for l in lo]
+    bound = [[l, l + (n - 1.5) * voxel] for l in lo]        # n points: half a voxel short, so rounding cannot add one
     vol = TSDFVolume(bound, voxel, device=DEV)
     assert vol.dims == (n, n, n), vol.dims
     return vol
