@@ -63,6 +63,10 @@ SIGNATURES = {
     "gs_tsdf_brick_flags_bytes": (c_size_t, [c_int] * 3),
     "gs_tsdf_brick_flags": (c_int, [_P, c_int, c_int, c_int, _P, _P]),
     "gs_tsdf_raycast": (c_int, [_P] * 3 + [c_int] * 3 + [_P, _P] + [c_int] * 3 + [c_float] * 12 + [_P] * 4),
+    "gs_tsdf_align_chunk": (c_int, []),
+    "gs_tsdf_align_workspace_bytes": (c_size_t, [c_int] * 4),
+    "gs_tsdf_align_system": (c_int, [_P, _P] + [c_int] * 3 + [_P, _P, _P] + [c_int] * 5 + [c_float] * 11 + [_P, _P, _P]),
+    "gs_tsdf_align_step": (c_int, [_P, _P, c_int, ctypes.c_double, ctypes.c_double, c_int, _P, _P]),
     "gs_esdf_build": (c_int, [_P, _P, c_int, c_int, c_int, c_float, c_int, c_float, _P, _P, _P, _P]),
     "gs_esdf_query": (c_int, [_P, _P] + [c_int] * 3 + [c_float] * 4 + [_P, c_int, _P, _P, _P, _P]),
     "gs_esdf_slice": (c_int, [_P] * 3 + [c_int] * 8 + [_P, _P, _P]),

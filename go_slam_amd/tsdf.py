@@ -25,6 +25,11 @@ csrc/frontier.hip answers what has not been seen: `ESDF.frontiers` groups the fr
 never-observed space into clusters, each priced by the route to it, and `ESDF.explore` picks one and plans the way there
 (frontier.py: marking, labelling and the cluster table; tests/frontier_restatement.py).
 
+csrc/tsdf_align.hip answers where a camera is: `TSDFVolume.align` moves given poses until a depth image's pixels lie on
+the volume's surface, `pose_scores` measures the fit, `localize.relocalize` finds a pose among candidates, `save` / `load`
+carry a volume to another run, and metrics_tsdf_align.txt reports how far a run's poses disagree with the surface they
+produced (localize.py; tests/tsdf_align_restatement.py).
+
 tsdf_live.py keeps such a volume during a run, while the poses still move; it fuses through
 `keyframe_observations`, the rule `fuse_keyframes` applies per chunk.
 """
@@ -36,6 +41,7 @@ import torch
 
 from . import _lib
 from . import frontier as _frontier
+from . import localize as _localize
 from . import plan as _plan
 from . import view as _view
 from .lietorch_shim import SE3
@@ -231,6 +237,30 @@ class TSDFVolume:
                     _lib.ptr(rgb), _lib.stream_ptr(dev))
             _lib.check(rc, what)
         return {"depth": depth, "normal": normal, "color": rgb}
+
+    def align(self, depth, c2w_init, intrinsics, frame=None, levels=_localize.DEFAULT_LEVELS, huber=0.5,
+              max_depth=math.inf, min_weight=1.0, lam_rel=1e-6, lam_abs=1e-9, min_count=64):
+        """Where were these depth images taken from?  B camera-to-world poses refined by direct alignment to this volume
+        (gs_tsdf_align_system / gs_tsdf_align_step), coarse to fine over `levels` = (pixel stride, iterations) pairs: see
+        `localize.align` for the arguments and the returned dict (c2w, ok, rmse_m, inlier_fraction, count, trace, moved_m,
+        moved_deg; host arrays, one read)."""
+        return _localize.align(self, depth, c2w_init, intrinsics, frame, levels, huber, max_depth, min_weight, lam_rel,
+                               lam_abs, min_count)
+
+    def pose_scores(self, depth, c2w, intrinsics, frame=None, stride=4, huber=0.5, max_depth=math.inf, min_weight=1.0):
+        """How well do these poses explain the depth images?  One gs_tsdf_align_system per pose and no step ->
+        {"rmse_m", "inlier_fraction", "count"} (`localize.pose_scores`)."""
+        return _localize.pose_scores(self, depth, c2w, intrinsics, frame, stride, huber, max_depth, min_weight)
+
+    def save(self, path):
+        """Write the volume as one .npz (tsdf, weight, colors, lo, voxel, trunc, max_weight, dims); `load` gives the same
+        bits back."""
+        _localize.save_volume(self, path)
+
+    @classmethod
+    def load(cls, path, device=None):
+        """The volume `save` wrote, on `device`; ValueError for a file whose arrays disagree with its dims."""
+        return _localize.load_volume(cls, path, device)
 
     @torch.no_grad()
     def vertex_attr(self, verts, min_weight=1.0):
@@ -882,11 +912,25 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
     height, n_yaw, robot_radius, stride, snap, start, lam, min_gain_cells, min_solid_cells, max_unknown} (absent by
     default; start is a world point or "last", the default) the pose of ESDF.next_view into {output}/map/next_view.txt
     (view.next_view_text) and, when a view is found, its route into {output}/map/next_view_path.txt (plan.path_text;
-    `tsdf_next_view_found`, `tsdf_next_view_gain_m3` and `tsdf_next_view_candidates` in `stats`).  Returns the Mesh, or
-    None when the key is absent or disabled."""
+    `tsdf_next_view_found`, `tsdf_next_view_gain_m3` and `tsdf_next_view_candidates` in `stats`).  With
+    cfg["tsdf"]["save_volume"] the fused volume goes to {output}/mesh/tsdf_volume.npz (TSDFVolume.save), and with
+    cfg["tsdf"]["align"] = {enable, every, levels, huber, max_depth, min_count} (absent by default; rgbd mode only) every
+    `every`-th frame of `stream` is aligned to the fused volume from its pose in `c2w_list` (localize.align_stream, in
+    batches) into {output}/metrics_tsdf_align.txt (localize.align_text; `tsdf_align_moved_mean_m`,
+    `tsdf_align_moved_max_m`, `tsdf_align_moved_constrained_mean_m` -- the movement along the directions the surfaces in
+    view constrain, localize.constrained_movement -- and `tsdf_align_failed` in `stats`); another mode, or a missing
+    stream, is refused before anything is fused or written.  Returns the Mesh, or None when the key is absent or
+    disabled."""
     opt = slam.cfg.get("tsdf") or {}
     if not opt.get("enable", False):
         return None
+    al = opt.get("align") or {}
+    if al.get("enable", False):                             # refused before anything is fused or written
+        if slam.cfg.get("mode", "rgbd") != "rgbd":
+            raise ValueError(f"fuse_from_config: tsdf.align needs rgbd mode (mode is {slam.cfg.get('mode')!r}: "
+                             "no sensor depth to align)")
+        if stream is None or c2w_list is None:
+            raise ValueError("fuse_from_config: tsdf.align needs the stream and its camera-to-world poses")
     bound = opt.get("bound") or slam.cfg["mapping"]["bound"]
     min_weight = float(opt.get("min_weight", 1.0))
     vol, mesh = fuse_keyframes(slam.video, bound, float(opt.get("voxel_size", 0.05)), source=opt.get("source", "tracked"),
@@ -988,6 +1032,19 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
                              tsdf_next_view_candidates=res["n_candidates"])
             print(f"TSDF next view: cell {res['view_cell']!r}, yaw {res['yaw']!r}, gain_m3 {res['gain_m3']!r}, "
                   f"{res['n_candidates']} candidates, {res['n_qualified']} qualified")
+    if opt.get("save_volume", False):
+        vol.save(f"{slam.output}/mesh/tsdf_volume.npz")
+    if al.get("enable", False):
+        res = _localize.align_stream(vol, stream, c2w_list, (slam.video.intrinsics[0] * 8).cpu().tolist(),
+                                     every=al.get("every", 5), out_path=f"{slam.output}/metrics_tsdf_align.txt",
+                                     levels=al.get("levels", _localize.DEFAULT_LEVELS), huber=al.get("huber", 0.5),
+                                     max_depth=al.get("max_depth", math.inf), min_count=al.get("min_count", 64),
+                                     min_weight=min_weight)
+        if stats is not None:
+            stats.update(tsdf_align_moved_mean_m=res["moved_mean_m"], tsdf_align_moved_max_m=res["moved_max_m"],
+                         tsdf_align_moved_constrained_mean_m=res["moved_constrained_mean_m"],
+                         tsdf_align_failed=res["n_failed"])
+        print("TSDF align: " + ", ".join(f"{k} {res[k]!r}" for k in _localize.ALIGN_REPORT_ORDER))
     meshing = slam.cfg.get("meshing") or {}
     gt_path = meshing.get("gt_mesh_path") or ""
     if meshing.get("eval_rec") and gt_path.find(".ply") > -1 and os.path.exists(gt_path) and len(mesh.faces) > 0:

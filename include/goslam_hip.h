@@ -351,6 +351,77 @@ int gs_tsdf_raycast(const float* tsdf, const float* weight, const float* colors,
                     float cy, float lo_x, float lo_y, float lo_z, float voxel, float near, float far, float step_voxels,
                     float min_weight, float* depth, float* normal, float* color, gs_stream_t stream);
 
+/* ---- alignment of depth images to that TSDF lattice: the Gauss-Newton system of the squared TSDF values at the
+ *      back-projected pixels and one damped step on the pose (no counterpart in the reference), csrc/tsdf_align.hip;
+ *      tests/tsdf_align_restatement.py restates it ----
+ *
+ * All fp32 and all fp64 arithmetic below is one rounding per operation, no fma; sqrt and / are correctly rounded.
+ *
+ * gs_tsdf_align_chunk: the number of sampled pixels one workgroup reduces.  It fixes the summation order below, so it
+ *   is part of the contract; callers and tests read it here.
+ * gs_tsdf_align_workspace_bytes: n_poses * ceil(S / chunk) * 32 * 8 with S = ceil(h / stride) * ceil(w / stride), the
+ *   chunks' partial rows; 0 for n_poses < 0, h, w or stride < 1, h * w > 2^30 or more than 2^31 - 1 rows.  Needs no GPU.
+ * gs_tsdf_align_system: tsdf, weight f32 [nx,ny,nz] as above, depth f32 [k,h,w], frame i32 [n_poses] on the device (the
+ *   depth map pose b looks at), pose f64 [n_poses,3,4] camera-to-world, rows (r0 r1 r2 o), workspace of at least
+ *   gs_tsdf_align_workspace_bytes, out f64 [n_poses,32]; every element of out is written.  Sizes in [2, 1024], n_poses,
+ *   k >= 0 (k >= 1 with a pose), h, w, stride >= 1, h * w <= 2^30, fx, fy != 0 and finite, cx, cy, lo finite, voxel > 0
+ *   finite, huber > 0, max_depth > 0 (+inf allowed), min_weight not NaN, no NULL pointer; anything else returns
+ *   GS_ERR_INVALID_ARG and launches nothing.  n_poses == 0 launches nothing.  frame lives on the device and is checked
+ *   there: a pose whose frame[b] lies outside [0, k) reads no depth and gets an all-zero row.
+ *   The sampled pixels of a pose are those with iu % stride == 0 && iv % stride == 0, sample s = (iv / stride) *
+ *   ceil(w / stride) + iu / stride.  Per pose (R, o) = (float) of each fp64 entry, and per sampled pixel:
+ *
+ *     d = depth[frame[b], iv, iu] ; considered += 1 if d > 0 ; skip unless 0 < d <= max_depth        (a NaN fails)
+ *     pc = ((float(iu) - cx) / fx * d, (float(iv) - cy) / fy * d, d)             (the quotient first, then times d)
+ *     q  = (r0 * pc.x + r1 * pc.y) + r2 * pc.z per row of R ; pw = q + o
+ *     g  = (pw - lo) / voxel ; a = floorf(g) ; skip unless 0 <= a < float(n - 1) on every axis (compared as floats) and
+ *          weight >= min_weight at all eight corners a + {0,1}^3: gs_tsdf_raycast's sample() ; fr = g - a
+ *     f  = trilinear tsdf and n = its gradient by gs_tsdf_raycast's lerp sequences (value: z, y, x; n.x: z, y; n.y: z,
+ *          x; n.z: y, x; lerp(p, q, s) = p + s * (q - p))
+ *     skip unless fabsf(f) < 1.0f                                        (a saturated sample carries no gradient)
+ *     gw = n / voxel per component
+ *     J  = (gw.x, gw.y, gw.z, q.y * gw.z - q.z * gw.y, q.z * gw.x - q.x * gw.z, q.x * gw.y - q.y * gw.x)
+ *          (the derivative of f under o' = o + v, R' = dR R: the rotation acts about the camera centre)
+ *     wt = fabsf(f) <= huber ? 1.0f : huber / fabsf(f)
+ *     in fp64: wj_i = (double)wt * (double)J_i ; H_ij += wj_i * (double)J_j for i <= j ; b_i += wj_i * (double)f ;
+ *              cost += ((double)wt * (double)f) * (double)f ; sq += (double)f * (double)f ; count += 1
+ *
+ *   out[b] = H (21: the upper triangle by rows, 00 01 .. 05 11 12 .. 55), b (6) at 21, cost at 27, count at 28, sq at
+ *   29, considered at 30, 0 at 31.  Order of every fp64 sum: chunk c holds the samples [c * chunk, (c + 1) * chunk);
+ *   within it thread t of 256 adds its samples t, t + 256, ... in increasing order onto 0.0 (a skipped sample adds
+ *   nothing), a wave adds its 64 partials by v += v[lane ^ m] for m = 32, 16, 8, 4, 2, 1, the four waves' totals are
+ *   added as ((w0 + w1) + w2) + w3 (gs_tsdf_frame_change's order), and the chunks' totals in increasing c starting from
+ *   chunk 0's.  count and considered are integers.  No atomics: two runs agree bitwise.  out is complete when the call's
+ *   work on the stream is.
+ * gs_tsdf_align_step: one Levenberg-damped Gauss-Newton step per pose from out [n_poses,32], on pose [n_poses,3,4] in
+ *   place; trace f64 [n_poses,4] or NULL receives (cost, count, considered, status) of the row it consumed.  lam_rel,
+ *   lam_abs >= 0 finite, min_count >= 1, else GS_ERR_INVALID_ARG.  In fp64, H_ji = H_ij:
+ *     A_ii = (H_ii + lam_rel * H_ii) + lam_abs ; A_ij = H_ij
+ *     for j = 0 .. 5: s = A_jj, then s = s - L_jk * L_jk for k = 0 .. j - 1 ; a pivot with !(s > 0) fails ;
+ *       L_jj = sqrt(s) ; for i > j: t = A_ij, then t = t - L_ik * L_jk for k = 0 .. j - 1 ; L_ij = t / L_jj
+ *     y_i = (b_i - L_i0 y_0 - .. - L_i,i-1 y_i-1) / L_ii for i = 0 .. 5 (terms subtracted in increasing k)
+ *     z_i = (y_i - L_5i z_5 - .. - L_i+1,i z_i+1) / L_ii for i = 5 .. 0 (terms subtracted in decreasing k) ; x = -z
+ *   status = 0 and the pose stays as it is when count < min_count or a pivot fails, else status = 1 and
+ *     o_i = o_i + x_i (i = 0, 1, 2) ; h = (x_3, x_4, x_5) * 0.5
+ *     len = sqrt(((1 + h.x * h.x) + h.y * h.y) + h.z * h.z) ; (a, b, c, d) = (1 / len, h.x / len, h.y / len, h.z / len)
+ *     dR = [ ((aa + bb) - cc) - dd   2 (bc - ad)             2 (bd + ac)           ]      aa = a * a, bc = b * c, ...
+ *          [ 2 (bc + ad)             ((aa - bb) + cc) - dd   2 (cd - ab)           ]      (a unit quaternion's matrix: a
+ *          [ 2 (bd - ac)             2 (cd + ab)             ((aa - bb) - cc) + dd ]      rotation, without trigonometry)
+ *     P_ij = (dR_i0 * R_0j + dR_i1 * R_1j) + dR_i2 * R_2j                         (P = dR R)
+ *     E_ij = ((P_0i * P_0j + P_1i * P_1j) + P_2i * P_2j) - (i == j ? 1 : 0)       (E = P^T P - I)
+ *     R_ij = P_ij - 0.5 * ((P_i0 * E_0j + P_i1 * E_1j) + P_i2 * E_2j)             (R = P (I - E / 2))
+ *   The last two lines are one Newton step toward the nearest rotation: the roundings of P would otherwise add up from
+ *   step to step (|R^T R - I| of 1e-14 after 100 steps); with it the departure stays below 5e-16 after any number.
+ *   An all-zero row (an out-of-range frame) has count 0 < min_count: status 0.                                         */
+int gs_tsdf_align_chunk(void);
+size_t gs_tsdf_align_workspace_bytes(int n_poses, int h, int w, int stride);
+int gs_tsdf_align_system(const float* tsdf, const float* weight, int nx, int ny, int nz, const float* depth,
+                         const int* frame, const double* pose, int n_poses, int k, int h, int w, int stride, float fx,
+                         float fy, float cx, float cy, float lo_x, float lo_y, float lo_z, float voxel, float max_depth,
+                         float min_weight, float huber, void* workspace, double* out, gs_stream_t stream);
+int gs_tsdf_align_step(const double* out, double* pose, int n_poses, double lam_rel, double lam_abs, int min_count,
+                       double* trace, gs_stream_t stream);
+
 /* ---- Euclidean distance field and 2-D occupancy map of that TSDF lattice (no counterpart in the reference),
  *      csrc/esdf.hip; tests/esdf_restatement.py restates it serially ----
  *
