@@ -13,6 +13,18 @@
 // `corr += s * T(w)`) with at::Half's compute-in-fp32-round-to-fp16 operator semantics, which makes
 // fp16 results bit-identical to the reference's fp16-accumulated values; the file is compiled with
 // -ffp-contract=off.
+//
+// Non-finite coordinates (one behaviour for every forward entry and radius): dx = x - floorf(x) is NaN for a NaN or
+// infinite x, so all four weights are NaN and every tap of every level of that pixel is NaN (0 x NaN on the taps outside
+// the plane, where safe_int puts the window) -- a failed track stays visible; no other pixel changes by a bit.  The
+// radius-3 kernels get this from their arithmetic; corr_index_generic_kernel, which skips taps outside the plane,
+// writes the NaN explicitly.  (The reference's saturating cast gives 0 for +-inf; nothing in the tracker relies on
+// that.)  corr_index_backward_kernel writes nothing for such a pixel.
+//
+// Judge: tests/test_lookup_numerics_gpu.py -- every entry point and load path below (tile8 with a straddled tile, the
+// clamped row-major load with its funnel shift, windows wholly outside, planes narrower than a window, the __int128 and
+// the element path, emit_nhwc's carries) against tests/lookup_referee.py: bit equality with the rounding chain written
+// as zero-padded bilinear sampling, and a derived bound against float64.
 #include "common.h"
 
 namespace {
@@ -472,7 +484,9 @@ __global__ __launch_bounds__(256) void corr_index_generic_kernel(
   const float dx = x0 - fx0, dy = y0 - fy0;
   const T* slice = vol + ((size_t)n * hw1 + p) * (size_t)(h2 * w2);
   T* out = corr + (size_t)n * rd * rd * hw1 + p;
-  for (int c = 0; c < rd * rd; ++c) out[(size_t)c * hw1] = (T)0;
+  // a non-finite coordinate: NaN in every tap, as the radius-3 kernels compute it (dx * dy is NaN exactly then)
+  const T fill = (dx * dy != dx * dy) ? (T)__builtin_nanf("") : (T)0;
+  for (int c = 0; c < rd * rd; ++c) out[(size_t)c * hw1] = fill;
   for (int i = 0; i < rd + 1; ++i) {
     for (int j = 0; j < rd + 1; ++j) {
       const int x1 = safe_int(fx0) - r + i, y1 = safe_int(fy0) - r + j;

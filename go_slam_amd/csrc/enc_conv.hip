@@ -18,6 +18,10 @@
 //     conv -> bias-add as two fp16 tensors) -> wave-private LDS transpose -> 16-byte stores of contiguous channel runs.
 //
 // The instance-norm / ReLU / residual tail of every convolution stays in gs_norm_act (instnorm.hip).
+//
+// Judge: tests/test_gemm_numerics_gpu.py::test_enc_conv_per_element -- all ten layer shapes, strided rows, odd maps and
+// partial pixel groups, with and without the fp16 bias, against the float64 convolution of tests/gemm_referee.py
+// (conv_ref): the worst-case fp32 bound plus the flip-share and excess gates measured against an fp32 CPU baseline.
 #include "common.h"
 
 namespace {

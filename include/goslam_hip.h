@@ -54,7 +54,15 @@ int gs_timing_names(char* buf, int buf_bytes);
 
 /* droid_backends.corr_index_forward (src/lib/droid.cpp:149-158, correlation_kernels.cu:19-70,
  * 126-155).  volume [n,h1,w1,h2,w2] (dtype), coords f32 [n,2,h1,w1] -> corr [n,2r+1,2r+1,h1,w1]
- * (dtype).  Arithmetic is carried in `dtype` in the reference's accumulation order.        */
+ * (dtype).  Arithmetic is carried in `dtype` in the reference's accumulation order: per tap
+ * ((s00 w_se + s01 w_sw) + s10 w_ne) + s11 w_nw, the fp32 weights cast to `dtype`, one rounding
+ * per operation, cells outside the plane read as 0 (the sign of a zero result is not specified).
+ * Non-finite coordinates -- this entry for every radius, gs_corr_lookup_pyramid[_slots] and
+ * gs_corr_lookup_enc[_slots] alike: a pixel whose x or y is NaN or +-inf gets NaN in EVERY tap of
+ * every level (its weights are NaN), and no other pixel changes by a bit.  (The reference's
+ * saturating cast returns 0 for +-inf; NaN keeps a failed track visible.)  gs_corr_index_backward
+ * adds nothing to the volume gradient for such a pixel.
+ * Judge: tests/test_lookup_numerics_gpu.py against the float64 model of tests/lookup_referee.py. */
 int gs_corr_index_forward(const void* volume, const float* coords, void* corr,
                           int n, int h1, int w1, int h2, int w2, int radius, int dtype,
                           gs_stream_t stream);

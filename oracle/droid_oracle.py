@@ -65,7 +65,11 @@ def corr_index_forward(volume, coords, r):
 
     The arithmetic is carried in the volume's dtype exactly as the kernel does
     (`corr += s * scalar_t(w)`, i outer / j inner), so for fp16 volumes the result is the
-    reference's fp16-accumulated value, not an fp32 sum rounded once."""
+    reference's fp16-accumulated value, not an fp32 sum rounded once.
+
+    Finite coordinates only restate those lines.  For a NaN or infinite coordinate this function returns NaN in all
+    (2r+1)^2 taps (zero taps times NaN weights), which is the package's documented behaviour (include/goslam_hip.h),
+    NOT the reference's: its saturating cast (:49-52) puts +-inf outside the plane and the skipped taps leave 0."""
     N, h1, w1, h2, w2 = volume.shape
     dt = volume.dtype
     rd = 2 * r + 1
@@ -75,7 +79,7 @@ def corr_index_forward(volume, coords, r):
     fy0 = torch.floor(y0)
     dx = x0 - fx0
     dy = y0 - fy0
-    w_nw = (dx * dy).to(dt)                       # scalar_t(dx*dy)
+    w_nw = (dx * dy).to(dt)                      # scalar_t(dx*dy)
     w_ne = (dx * (1.0 - dy)).to(dt)               # scalar_t(dx*(1-dy))   [i>0, j<rd]
     w_sw = ((1.0 - dx) * dy).to(dt)               # scalar_t((1-dx)*dy)   [i<rd, j>0]
     w_se = ((1.0 - dx) * (1.0 - dy)).to(dt)

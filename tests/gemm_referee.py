@@ -21,7 +21,9 @@ can round the intermediate value to the other neighbour than the reference does 
 boundary from the float64 one) and is then off by a whole ulp of the intermediate, ~1e-4 of mag: the baseline does the
 same on a few elements in 10^4, so its own max excess is that large and the MAX-excess gate is blunt for such an
 operation; the flip share and the p99.9 excess stay sharp (with bias + ReLU a truncating last conversion gives 0.24 --
-half of the outputs the ReLU leaves -- and 1.5e-5 .. 4.4e-5, tests/test_gemm_referee_cpu.py)."""
+half of the outputs the ReLU leaves -- and 1.5e-5 .. 4.4e-5, tests/test_gemm_referee_cpu.py).  At C = 128 the hard bound's
+K 2^-23 mag term happens to cover that whole ulp; for the shorter sums of the frame encoders (K = 32 .. 288 with an fp16
+bias) it does not, and `two_step_slack` adds it for exactly the elements that can round either way (`slack`)."""
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -42,11 +44,27 @@ def ulp16(r):
     return np.exp2(np.floor(np.log2(a)) - 10.0)
 
 
-def hard_bound(ref, mag, K):
-    return 0.5 * ulp16(ref) * (1.0 + 2.0 ** -10) + K * 2.0 ** -23 * mag
+def hard_bound(ref, mag, K, slack=None):
+    b = 0.5 * ulp16(ref) * (1.0 + 2.0 ** -10) + K * 2.0 ** -23 * mag
+    return b if slack is None else b + slack
 
 
-def measure(y16, ref, mag, K, where=None):
+def two_step_slack(pre_ref, pre_mag, K, ref):
+    """The allowance of a two-step operation whose K is too small for the hard bound's K 2^-23 mag term to cover an
+    intermediate rounding that lands on the other neighbour (see `two_step`; at K = 32 .. 288 even the fp32 baseline
+    misses the unwidened bound, by up to 1.7 x).  Only an element whose float64 intermediate lies within the fp32
+    summation error (2 K 2^-23 mag, the hard bound's own term) of an fp16 rounding boundary can round the other way; it
+    is then off by one spacing of the intermediate, and the last rounding acts on that other value: slack =
+    ulp16(pre) + 1/2 ulp16(ref) there and 0 on every other element, for which the bound stays as it is.  That is 5 % of
+    the elements at K = 32 but nearly all from K ~ 200 on (the worst-case fp32 error is then as large as the spacing):
+    there the hard bound is ~1.5 ulp and blunt, the flip share and the p99.9 excess stay sharp, and the GPU test pins
+    the second rounding exactly (the CPU's fp16 add applied to the kernel's own bias-free output)."""
+    dist = 0.5 * ulp16(pre_ref) - np.abs(pre_ref - round16(pre_ref))
+    near = dist <= 2.0 * K * 2.0 ** -23 * pre_mag
+    return np.where(near, ulp16(pre_ref) + 0.5 * ulp16(ref), 0.0)
+
+
+def measure(y16, ref, mag, K, where=None, slack=None):
     """(flip share, max excess, p99.9 excess, largest |y - ref| / hard bound) over the elements with finite round16(ref)
     (and, with `where`, inside that mask)"""
     y = np.asarray(y16).astype(np.float64).reshape(-1)
@@ -58,10 +76,11 @@ def measure(y16, ref, mag, K, where=None):
         sel = sel & np.asarray(where, dtype=bool).reshape(-1)
     assert sel.any(), "no finite reference element"
     y, ref, mag, r16 = y[sel], ref[sel], mag[sel], r16[sel]
+    slack = None if slack is None else np.asarray(slack, dtype=np.float64).reshape(-1)[sel]
     with np.errstate(invalid="ignore"):
         err = np.abs(y - ref)
     err = np.where(np.isfinite(y), err, np.inf)
-    bound = hard_bound(ref, mag, K)
+    bound = hard_bound(ref, mag, K, slack)
     over = np.maximum(0.0, err - 0.5 * ulp16(ref))
     with np.errstate(divide="ignore", invalid="ignore"):
         x = np.where(over > 0.0, over / mag, 0.0)
@@ -69,11 +88,11 @@ def measure(y16, ref, mag, K, where=None):
             "hard": float((err / bound).max()), "worst": int(np.flatnonzero(sel)[int(np.argmax(err / bound))])}
 
 
-def gate(y16, ref, mag, K, baseline16, label="", where=None):
+def gate(y16, ref, mag, K, baseline16, label="", where=None, slack=None):
     """asserts the three bounds of the module's docstring; returns the six measured numbers (kernel and baseline: flip
     share, max excess, p99.9 excess) and both largest ratios to the hard bound"""
-    k = measure(y16, ref, mag, K, where)
-    b = measure(baseline16, ref, mag, K, where)
+    k = measure(y16, ref, mag, K, where, slack)
+    b = measure(baseline16, ref, mag, K, where, slack)
     res = {"flip": k["flip"], "flip_base": b["flip"], "max": k["max"], "max_base": b["max"], "p999": k["p999"],
            "p999_base": b["p999"], "hard": k["hard"], "hard_base": b["hard"], "worst": k["worst"]}
     res["line"] = (f"{label}: flips {k['flip']:.3e} (base {b['flip']:.3e})  max excess {k['max']:.2e} ({b['max']:.2e})  "
@@ -84,9 +103,9 @@ def gate(y16, ref, mag, K, baseline16, label="", where=None):
     return res
 
 
-def failed_assertions(y16, ref, mag, K, baseline16):
+def failed_assertions(y16, ref, mag, K, baseline16, slack=None):
     """which of the gate's assertions a result misses: a subset of {"hard", "flip", "excess"}"""
-    return _missed(measure(y16, ref, mag, K), measure(baseline16, ref, mag, K))
+    return _missed(measure(y16, ref, mag, K, slack=slack), measure(baseline16, ref, mag, K, slack=slack))
 
 
 def _missed(k, b):
@@ -138,6 +157,39 @@ def conv3x3_ref(x16, w16):
         mag = _conv(x16.double().abs(), w16.double().abs()).numpy()
         base = _conv(x16.float(), w16.float()).half().numpy()
     return ref, mag, 9 * x16.shape[-1], base
+
+
+def conv_ref(x16, w16, ksize, stride, bias=None, relu=False, with_slack=False):
+    """(ref, mag, K, baseline16[, slack]) of act(conv(x) + b) as [n,ho,wo,O]: NHWC fp16 x [n,h,w,C], fp16 w [O,C,k,k], padding
+    ksize // 2, stride 1 or 2; K = ksize^2 C counts the terms of an interior pixel.  The bias joins where the kernels
+    document it, told by its dtype:
+      fp16 bias (gs_enc_conv): added AFTER the fp16 rounding of the convolution, half(half(conv) + b) -- `two_step`;
+      fp32 bias (gs_conv7x7_c4): in the fp32 accumulator before the ONE rounding, K + 1 terms.
+    ReLU commutes with the last rounding and is applied to the reference and the baseline alike.  with_slack: also the
+    gate's `slack` (two_step_slack for the fp16 bias, None otherwise)."""
+    assert w16.shape[2] == w16.shape[3] == ksize and x16.dtype == torch.float16 and w16.dtype == torch.float16
+
+    def cv(x, w):
+        return F.conv2d(x.permute(0, 3, 1, 2), w, stride=stride, padding=ksize // 2).permute(0, 2, 3, 1).contiguous()
+
+    with np.errstate(all="ignore"):
+        ref = cv(x16.double(), w16.double()).numpy()
+        mag = cv(x16.double().abs(), w16.double().abs()).numpy()
+        base32 = cv(x16.float(), w16.float())
+    K = ksize * ksize * x16.shape[-1]
+    act = (lambda p: np.maximum(p, 0.0)) if relu else (lambda p: p)
+    extra = (None,) if with_slack else ()
+    if bias is None:
+        return (act(ref), mag, K, torch.relu(base32).half().numpy() if relu else base32.half().numpy()) + extra
+    b64 = bias.double().numpy()
+    if bias.dtype == torch.float16:
+        pre, pmag = ref, mag
+        ref, base = two_step(pre, base32.half().numpy(), lambda p: act(p + b64))
+        extra = (two_step_slack(pre, pmag, K, ref),) if with_slack else ()
+        return (ref, pmag + np.abs(b64), K + 1, base) + extra
+    assert bias.dtype == torch.float32
+    base32 = base32 + bias
+    return (act(ref + b64), mag + np.abs(b64), K + 1, (torch.relu(base32) if relu else base32).half().numpy()) + extra
 
 
 def two_step(pre_ref, pre_base, fn):

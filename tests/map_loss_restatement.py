@@ -170,7 +170,9 @@ def run_sharded(c, device, fused, monkeypatch, model):
             t.copy_(torch.tensor([c["count"], c["n_rays_global"]], dtype=t.dtype))
         return t
     monkeypatch.setattr(D, "all_reduce_sum_", fake_all_reduce)
-    leaf = lambda k: c[k].to(device).requires_grad_(True)
+    # (a copy: on the CPU `.to` returns the case's own tensor, and marking THAT as requiring gradients made every later
+    # run on another device -- the GPU tests after the CPU tests in one session -- a non-leaf without .grad)
+    leaf = lambda k: c[k].detach().clone().to(device).requires_grad_(True)
     ret = {"color": leaf("color"), "depth": leaf("depth"), "depth_variance": leaf("depth_variance"), "sdf": leaf("sdf"),
            "z_vals": c["z_vals"].to(device), "gradient_error": leaf("gradient_error")}
     loss, glob = D.mapping_loss_sharded(ret, c["rays_color"].to(device), c["rays_depth"].to(device),

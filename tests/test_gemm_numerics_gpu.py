@@ -1,12 +1,42 @@
 """The implicit-GEMM kernels of the update operator and of the correlation path against float64, per element.
 
 gs_conv3x3_pp and its bias + ReLU / merged-head epilogues, gs_conv1x1, gs_corr_lookup_enc, level 0 of
-gs_corr_volume_pyramid and gs_altcorr_pyramid each run on seeded fp16 operands; tests/gemm_referee.py computes, on the CPU
+gs_corr_volume_pyramid, gs_altcorr_pyramid, gs_enc_conv (all ten layer shapes of the frame encoders) and gs_conv7x7_c4
+(the flow encoder's stem) each run on seeded fp16 operands; tests/gemm_referee.py computes, on the CPU
 and from the same fp16 operands, the float64 result, its magnitude sum and an fp32 baseline, and its `gate` asserts the
 worst-case fp32 bound plus the two statistical bounds (rounding flips, excess over half an ulp) that separate "another
 summation order" from "a rounding the kernel's header does not document" -- tests/test_gemm_referee_cpu.py shows that an
-fp16 accumulator hand-over, a truncating conversion and an unpadded image seam fail them.  Nothing computed on the GPU
-acts as referee.  Every gate prints its figures (kernel and baseline side by side)."""
+fp16 accumulator hand-over, a truncating conversion, an unpadded image seam, a stem that drops a border-straddling tap
+pair and a stride-2 kernel on the odd pixels fail them.  Nothing computed on the GPU acts as referee.  Every gate prints
+its figures (kernel and baseline side by side).  The window lookups whose features gs_corr_lookup_enc multiplies have
+their own judge, tests/test_lookup_numerics_gpu.py.
+
+MEASURED for gs_enc_conv and gs_conv7x7_c4 (MI355X; kernel (baseline), the largest over the runs of a row):
+  (k, c_in, c_out, stride)     bias      gates  flip share          max excess          p99.9 excess        hard-bound ratio
+  enc_conv (7, 4, 32, 2)       no bias     6    6.2e-04 (1.6e-03)   1.6e-08 (3.9e-08)   0.0e+00 (2.5e-09)   0.861 (0.861)
+  enc_conv (7, 4, 32, 2)       fp16 bias   6    5.4e-04 (8.9e-04)   6.0e-05 (8.4e-05)   0.0e+00 (0.0e+00)   0.942 (0.942)
+  enc_conv (3, 32, 32, 1)      no bias     4    1.6e-02 (3.3e-02)   2.2e-08 (6.1e-08)   8.4e-09 (3.0e-08)   0.784 (0.784)
+  enc_conv (3, 32, 32, 1)      fp16 bias   4    3.0e-03 (7.0e-03)   4.6e-05 (6.8e-05)   4.9e-07 (5.8e-07)   0.792 (0.792)
+  enc_conv (3, 32, 64, 2)      no bias     4    1.2e-02 (2.7e-02)   1.4e-08 (8.1e-08)   7.1e-09 (2.5e-08)   0.788 (0.788)
+  enc_conv (3, 32, 64, 2)      fp16 bias   4    2.4e-03 (5.7e-03)   7.2e-05 (8.9e-05)   1.4e-07 (6.2e-07)   0.845 (0.845)
+  enc_conv (3, 64, 64, 1)      no bias     4    2.2e-02 (4.7e-02)   2.6e-08 (8.5e-08)   1.0e-08 (3.4e-08)   0.599 (0.599)
+  enc_conv (3, 64, 64, 1)      fp16 bias   4    4.3e-03 (9.7e-03)   5.5e-05 (9.3e-05)   4.0e-07 (6.8e-07)   0.444 (0.487)
+  enc_conv (3, 64, 128, 2)     no bias     4    1.6e-02 (3.7e-02)   2.1e-08 (7.9e-08)   8.0e-09 (2.9e-08)   0.607 (0.607)
+  enc_conv (3, 64, 128, 2)     fp16 bias   4    2.9e-03 (8.9e-03)   3.0e-05 (3.0e-05)   2.0e-07 (5.9e-07)   0.309 (0.336)
+  enc_conv (3, 128, 128, 1)    no bias     6    2.8e-02 (6.0e-02)   2.9e-08 (1.2e-07)   1.0e-08 (3.2e-08)   0.349 (0.349)
+  enc_conv (3, 128, 128, 1)    fp16 bias   6    5.6e-03 (1.5e-02)   5.6e-05 (5.6e-05)   2.8e-07 (5.0e-07)   0.400 (0.400)
+  enc_conv (1, 32, 64, 2)      no bias     4    1.0e-02 (1.7e-02)   2.1e-08 (3.4e-08)   8.8e-09 (1.7e-08)   0.981 (0.981)
+  enc_conv (1, 32, 64, 2)      fp16 bias   4    1.4e-03 (2.7e-03)   2.2e-04 (2.2e-04)   2.4e-07 (3.7e-07)   0.987 (0.987)
+  enc_conv (1, 64, 128, 2)     no bias     4    1.4e-02 (2.4e-02)   2.0e-08 (5.0e-08)   8.2e-09 (2.4e-08)   0.962 (0.962)
+  enc_conv (1, 64, 128, 2)     fp16 bias   4    2.6e-03 (4.2e-03)   8.6e-05 (9.7e-05)   4.7e-07 (9.7e-07)   0.967 (0.967)
+  enc_conv (1, 128, 128, 1)    no bias     4    1.6e-02 (3.1e-02)   3.1e-08 (9.7e-08)   9.1e-09 (2.6e-08)   0.912 (0.912)
+  enc_conv (1, 128, 128, 1)    fp16 bias   4    2.9e-03 (5.6e-03)   1.2e-04 (2.3e-04)   3.9e-07 (8.1e-07)   0.939 (0.939)
+  enc_conv (1, 128, 256, 1)    no bias     4    1.6e-02 (3.1e-02)   3.2e-08 (8.3e-08)   9.1e-09 (2.8e-08)   0.913 (0.913)
+  enc_conv (1, 128, 256, 1)    fp16 bias   4    2.5e-03 (5.9e-03)   2.3e-04 (2.6e-04)   4.0e-07 (8.0e-07)   0.935 (0.935)
+  conv7x7_c4                   fp32 bias  12    6.3e-03 (1.1e-02)   2.1e-07 (1.2e-07)   6.2e-09 (1.8e-08)   0.948 (0.948)
+  With the fp16 bias the max excess is an intermediate rounding on the other neighbour (the baseline's is as large) and
+  the hard bound carries gemm_referee.two_step_slack; the second rounding itself is asserted exactly.  None of these
+  figures is a tolerance: the bounds are the gate's own factors over the CPU baseline."""
 import numpy as np
 import pytest
 import torch
@@ -233,7 +263,7 @@ def _features(n, h, w, seed, scale=1.5):
 @pytest.mark.parametrize("h,w,tile8", [(12, 20, False), (16, 32, True)])
 def test_corr_lookup_enc_per_element(built_lib, h, w, tile8):
     """gs_corr_lookup_enc = relu(W feat + b) over the 196 looked-up features (K = 197).  The features are those of
-    gs_corr_lookup_pyramid on the same volumes and coordinates (bit-exact against the oracle elsewhere); the product is
+    gs_corr_lookup_pyramid on the same volumes and coordinates (judged by tests/test_lookup_numerics_gpu.py); the product is
     refereed on the CPU.  Coordinates: identity + 6 px of noise, n = 2."""
     from go_slam_amd import droid_backends as db
     from go_slam_amd.corr import CorrBlock
@@ -380,3 +410,101 @@ def test_altcorr_pyramid_per_element(built_lib, case):
     ref, mag, K, base = R.altcorr_ref(pyr, coords[0], ii, jj)
     assert K == 132 and float((mag > 0).mean()) > 0.3                  # (the rest: windows of the coarse levels outside)
     _report(R.gate(y.numpy(), ref, mag, K, base, label=f"altcorr_pyramid {case}"))
+
+
+# ------------------------------------------------------------------------------------------------ gs_enc_conv
+
+# (ksize, c_in, c_out, stride): the ten layer shapes the kernel is built for (include/goslam_hip.h)
+ENC_SHAPES = [(7, 4, 32, 2), (3, 32, 32, 1), (3, 32, 64, 2), (3, 64, 64, 1), (3, 64, 128, 2), (3, 128, 128, 1),
+              (1, 32, 64, 2), (1, 64, 128, 2), (1, 128, 128, 1), (1, 128, 256, 1)]
+# 2 x 7 x 37: stride 1 -> one full and one 5-pixel group per row, stride 2 -> 4 x 19 from odd sizes, two images;
+# 1 x 9 x 70: stride 2 -> 35 outputs per row
+ENC_MAPS = [(2, 7, 37), (1, 9, 70)]
+
+
+def _enc_operands(regime, shape, fmap, seed):
+    k, cin, cout, stride = shape
+    n, h, w = fmap
+    x, wt = R.operands(regime, (n, h, w, cin), (cout, cin, k, k), (k * k * cin) ** 0.5, seed=seed)
+    if k == 7:                                  # the stem reads RGB0: the fourth channel and its weights are zero
+        x[..., 3] = 0
+        wt[:, 3] = 0
+    return x, wt
+
+
+def _run_enc_conv(x, wt, shape, bias16):
+    """gs_enc_conv on the first c_in channels of rows c_in + 8 apart (the stem: dense, as the entry demands) into rows
+    c_out + 8 apart; the 8 sentinel columns are checked"""
+    from go_slam_amd import _lib
+    from go_slam_amd.extractor import pack_enc_conv_weight
+    k, cin, cout, stride = shape
+    n, h, w, _ = x.shape
+    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+    xs = cin if k == 7 else cin + 8
+    xbuf = _strided(x, xs)
+    wp = pack_enc_conv_weight((wt[:, :3] if k == 7 else wt).to(DEV))
+    assert wp.numel() == _lib.lib().gs_enc_conv_wpack_elems(k, cin, cout)
+    bd = None if bias16 is None else bias16.to(DEV)
+    y = torch.full((n, ho, wo, cout + 8), SENTINEL, dtype=torch.float16, device=DEV)
+    rc = _lib.lib().gs_enc_conv(_lib.ptr(xbuf), xs, cin, _lib.ptr(wp), _lib.ptr(bd), _lib.ptr(y), cout + 8, cout, k, stride,
+                                n, h, w, None, None, _lib.stream_ptr(DEV))
+    _lib.check(rc, "enc_conv")
+    torch.cuda.synchronize()
+    y = y.cpu()
+    assert bool((y[..., cout:] == SENTINEL).all()), "the kernel wrote outside its channels"
+    return y[..., :cout].contiguous()
+
+
+@pytest.mark.parametrize("fmap", ENC_MAPS, ids=lambda v: "x".join(map(str, v)))
+@pytest.mark.parametrize("shape", ENC_SHAPES, ids=lambda v: "x".join(map(str, v)))
+def test_enc_conv_per_element(built_lib, shape, fmap):
+    """csrc/enc_conv.hip, every layer shape: fp32 accumulation and one fp16 rounding; with the fp16 bias a second rounding
+    after the fp16 add (gemm_referee.conv_ref rounds where the kernel does, `two_step`, and gives the hard bound the
+    allowance of gemm_referee.two_step_slack).  plain and offset on every shape, subnormal inputs on the stem and on
+    3 x 3 128 -> 128."""
+    k, cin, cout, stride = shape
+    regimes = ["plain", "offset"] + (["subnormal"] if shape in (ENC_SHAPES[0], ENC_SHAPES[5]) else [])
+    bias16 = (0.3 * torch.randn(cout, generator=torch.Generator().manual_seed(1210 + cout))).half()
+    for regime in regimes:
+        x, wt = _enc_operands(regime, shape, fmap, seed=1200 + 10 * k + cin + cout + fmap[2])
+        if regime == "subnormal":
+            assert float(x.float().max()) < 2.0 ** -14
+        for bias in (None, bias16):
+            ref, mag, K, base, slack = R.conv_ref(x, wt, k, stride, bias, with_slack=True)
+            assert K == k * k * cin + (bias is not None)
+            y = _run_enc_conv(x, wt, shape, bias)
+            assert tuple(y.shape) == ref.shape
+            if bias is None:
+                plain_y = y
+            else:           # the second rounding, exactly: the CPU's fp16 add on the kernel's own (gated) bias-free output
+                assert torch.equal(y, (plain_y.float() + bias.float()).half())
+            _report(R.gate(y.numpy(), ref, mag, K, base, slack=slack,
+                           label=f"enc_conv {shape} {fmap} {regime} {'fp16 bias' if bias is not None else 'no bias'}"))
+
+
+# ------------------------------------------------------------------------------------------------ gs_conv7x7_c4
+
+@pytest.mark.parametrize("n,h,w,rt", [(1, 7, 9, 3), (2, 23, 37, 5)])
+@pytest.mark.parametrize("relu", [False, True])
+def test_conv7x7_c4_per_element(built_lib, n, h, w, rt, relu):
+    """csrc/conv7x7.hip: the fp32 accumulators start at the fp32 bias, one rounding to fp16, ReLU: K = 196 + 1.  A 7 x 9
+    map in strips of 3 rows (a last strip of one row, every pixel within 3 of a border) and 2 x 23 x 37 in strips of 5."""
+    from go_slam_amd import _lib
+    from go_slam_amd.droid_net import pack_conv7x7_c4_weight
+    bias = 0.3 * torch.randn(128, generator=torch.Generator().manual_seed(1310))
+    for regime in ("plain", "offset", "subnormal"):
+        x, wt = R.operands(regime, (n, h, w, 4), (128, 4, 7, 7), 14.0, seed=1300 + h + w)
+        ref, mag, K, base = R.conv_ref(x, wt, 7, 1, bias, relu)
+        assert K == 197
+        xd, wp, bd = x.to(DEV), pack_conv7x7_c4_weight(wt.to(DEV)), bias.to(DEV)
+        y = torch.full((n, h, w, 128 + 8), SENTINEL, dtype=torch.float16, device=DEV)
+        rc = _lib.lib().gs_conv7x7_c4(_lib.ptr(xd), _lib.ptr(wp), _lib.ptr(bd), _lib.ptr(y), 128 + 8, n, h, w, int(relu), rt,
+                                      _lib.stream_ptr(DEV))
+        _lib.check(rc, "conv7x7_c4")
+        torch.cuda.synchronize()
+        y = y.cpu()
+        assert bool((y[..., 128:] == SENTINEL).all()), "the kernel wrote outside its channels"
+        got = y[..., :128].contiguous().numpy()
+        if relu:
+            assert 0.05 < float((got == 0).mean()) < 0.95
+        _report(R.gate(got, ref, mag, K, base, label=f"conv7x7_c4 {n}x{h}x{w} rt={rt} relu={int(relu)} {regime}"))

@@ -114,3 +114,82 @@ def test_two_step_operation_under_the_unchanged_bounds(n_out, regime):
     print(f"  truncating: flips {t['flip']:.3f}, p99.9 excess {t['p999']:.2e}, max {t['max']:.2e}, hard {t['hard']:.3f}")
     assert {"flip", "excess"} <= R.failed_assertions(R.truncate16(post), ref, mag, K + 1, base)
     assert t["p999"] > R.EXCESS_FACTOR * res["p999_base"] + R.EXCESS_FLOOR
+
+
+# ---------------------------------------------------------------------------------- encoder and stem convolutions
+
+def _stem_case(regime):
+    x, wt = R.operands(regime, (2, 7, 37, 4), (32, 4, 7, 7), 14.0, seed=1247)
+    x[..., 3] = 0
+    wt[:, 3] = 0
+    return x, wt
+
+
+@pytest.mark.parametrize("regime", ["plain", "offset"])
+def test_conv_ref_bias_points_and_a_correct_convolution_passes(regime):
+    """conv_ref's baseline is one rounding without bias, two with an fp16 bias (half(half(conv) + b)), one with an fp32
+    bias; an fp32 convolution summed in another order (channels-first taps) passes each gate"""
+    x, wt = R.operands(regime, (2, 7, 37, 32), (64, 32, 3, 3), 288 ** 0.5, seed=1232)
+    b16 = (0.3 * torch.randn(64, generator=torch.Generator().manual_seed(5))).half()
+    other = sum(torch.nn.functional.conv2d(x.float().permute(0, 3, 1, 2)[:, c:c + 1], wt.float()[:, c:c + 1], stride=2, padding=1)
+                for c in reversed(range(32))).permute(0, 2, 3, 1)
+    for bias in (None, b16, b16.float()):
+        ref, mag, K, base, slack = R.conv_ref(x, wt, 3, 2, bias, with_slack=True)
+        assert ref.shape == (2, 4, 19, 64) and K == 288 + (bias is not None)
+        if slack is not None:                                  # the allowance is needed: the baseline is a correct kernel
+            print(f"  two-step slack on {float((slack > 0).mean()):.2e} of the elements; without it the baseline is at "
+                  f"{R.measure(base, ref, mag, K)['hard']:.2f} of the hard bound")
+            assert bias.dtype == torch.float16 and bool((slack > 0).any())
+        if bias is None:
+            y = other.half()
+        elif bias.dtype == torch.float16:
+            y = (other.half().float() + bias.float()).half()
+        else:
+            y = (other + bias).half()
+        print(R.gate(y.numpy(), ref, mag, K, base, slack=slack,
+                     label=f"3x3 stride 2 {regime} bias {None if bias is None else bias.dtype}")["line"])
+    ref16, _, _, base16 = R.conv_ref(x, wt, 3, 2, b16)
+    ref32, _, _, base32 = R.conv_ref(x, wt, 3, 2, b16.float())
+    assert (base16 != base32).any() and (R.round16(ref16) != R.round16(ref32)).any()      # the bias point matters
+
+
+@pytest.mark.parametrize("regime", ["plain", "offset"])
+@pytest.mark.parametrize("mutant", ["stem drops the border-straddling tap pair", "stride 2 reads the odd pixels"])
+def test_wrong_encoder_convolutions_fail(regime, mutant):
+    """the stem's k-group is a PAIR of neighbouring taps (kx = 2 g, 2 g + 1) read as two 8-byte loads: a kernel that drops
+    the whole pair when one of its pixels lies outside the image loses the in-image tap of the pair in the border columns;
+    a stride-2 kernel that samples input pixels 2 o + 1 instead of 2 o shifts the whole output.  Both miss the hard
+    bound."""
+    if mutant.startswith("stem"):
+        x, wt = _stem_case(regime)
+        ref, mag, K, base = R.conv_ref(x, wt, 7, 2)
+        n, h, w, _ = x.shape
+        xp = torch.nn.functional.pad(x.float().permute(0, 3, 1, 2), (3, 3, 3, 3))
+        ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+        y = torch.zeros(n, 32, ho, wo)
+        for g in range(4):
+            for kx in (2 * g, 2 * g + 1):
+                if kx > 6:
+                    continue
+                ix = 2 * torch.arange(wo) - 3 + 2 * g                              # input column of the pair's first tap
+                keep = ((ix >= 0) & (ix + 1 < w)).float()                          # the pair lies wholly inside the image
+                for ky in range(7):
+                    patch = xp[:, :, ky:ky + 2 * ho - 1:2, kx:kx + 2 * wo - 1:2]    # [n,4,ho,wo]
+                    y += torch.einsum("nchw,oc->nohw", patch, wt.float()[:, :, ky, kx]) * keep
+        y = y.permute(0, 2, 3, 1).half().numpy()
+    else:
+        x, wt = R.operands(regime, (2, 7, 37, 32), (64, 32, 3, 3), 288 ** 0.5, seed=1232)
+        ref, mag, K, base = R.conv_ref(x, wt, 3, 2)
+        shifted = torch.nn.functional.pad(x.float(), (0, 0, 0, 1, 0, 1))[:, 1:, 1:]            # pixel (y, x) <- (y + 1, x + 1)
+        y = torch.nn.functional.conv2d(shifted.permute(0, 3, 1, 2), wt.float(), stride=2, padding=1).permute(0, 2, 3, 1)
+        y = y.half().numpy()
+    failed = R.failed_assertions(y, ref, mag, K, base)
+    k = R.measure(y, ref, mag, K)
+    print(f"{mutant} {regime}: fails {sorted(failed)}; flips {k['flip']:.3f}, hard {k['hard']:.3g}")
+    assert "hard" in failed and k["hard"] > 100.0
+    with pytest.raises(AssertionError):
+        R.gate(y, ref, mag, K, base)
+    if mutant.startswith("stem"):                      # only the border columns are wrong: the interior is a correct kernel
+        inner = np.zeros(ref.shape, dtype=bool)
+        inner[:, :, 2:-2] = True
+        assert R.measure(y, ref, mag, K, where=inner)["hard"] <= 1.0
