@@ -67,6 +67,11 @@ SIGNATURES = {
     "gs_tsdf_align_workspace_bytes": (c_size_t, [c_int] * 4),
     "gs_tsdf_align_system": (c_int, [_P, _P] + [c_int] * 3 + [_P, _P, _P] + [c_int] * 5 + [c_float] * 11 + [_P, _P, _P]),
     "gs_tsdf_align_step": (c_int, [_P, _P, c_int, ctypes.c_double, ctypes.c_double, c_int, _P, _P]),
+    "gs_tsdf_register_workspace_bytes": (c_size_t, [c_int] * 5),
+    "gs_tsdf_register_system": (c_int, ([_P, _P] + [c_int] * 3 + [c_float] * 5) * 2 + [_P, c_int, c_int, c_float, c_float,
+                                                                                     _P, _P, _P]),
+    "gs_tsdf_merge": (c_int, [_P] * 3 + [c_int] * 3 + [c_float] * 6 + [_P] * 3 + [c_int] * 3 + [c_float] * 5
+                      + [_P, c_float, _P]),
     "gs_esdf_build": (c_int, [_P, _P, c_int, c_int, c_int, c_float, c_int, c_float, _P, _P, _P, _P]),
     "gs_esdf_query": (c_int, [_P, _P] + [c_int] * 3 + [c_float] * 4 + [_P, c_int, _P, _P, _P, _P]),
     "gs_esdf_slice": (c_int, [_P] * 3 + [c_int] * 8 + [_P, _P, _P]),

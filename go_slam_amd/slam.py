@@ -213,7 +213,9 @@ class SLAM:
         depth, the means under `tsdf_*` keys of the returned statistics, and with cfg["tsdf"]["esdf"]["enable"]
         metrics_tsdf_clearance.txt, the clearance of the estimated camera centres in that volume's distance field, and
         with its `slice` key map/occupancy.pgm and .yaml, with its `plan` key map/path.txt, the collision-free route
-        between two points, by default from the last camera centre to the first (tsdf.fuse_from_config).  With cfg["tsdf"]["live"]["enable"] the
+        between two points, by default from the last camera centre to the first (tsdf.fuse_from_config), and with
+        cfg["tsdf"]["merge"]["enable"] mesh/tsdf_merged_mesh.ply and metrics_tsdf_merge.txt, this run's volume registered to
+        and joined with the one an earlier run saved (tsdf_merge.join_volumes).  With cfg["tsdf"]["live"]["enable"] the
         running volume is brought to the final poses (LiveFusion.finish) and meshed into mesh/tsdf_live_mesh.ply, and
         `tsdf_live_refused` (keyframes re-fused over the run) and `tsdf_live_keyframes` join the statistics.  With
         cfg["render_eval"]["enable"] (keys enable, every, save_images) and a map, also metrics_render.txt: PSNR, SSIM and depth L1 of the map's renderings against the input

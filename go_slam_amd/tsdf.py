@@ -30,6 +30,11 @@ the volume's surface, `pose_scores` measures the fit, `localize.relocalize` find
 carry a volume to another run, and metrics_tsdf_align.txt reports how far a run's poses disagree with the surface they
 produced (localize.py; tests/tsdf_align_restatement.py).
 
+csrc/tsdf_merge.hip puts two volumes together: `TSDFVolume.register` finds the transform that lays another volume's
+surfaces onto this one's, `TSDFVolume.merge` fuses another volume into this one, `tsdf_merge.join_volumes` makes one map
+of several sessions' volumes, and cfg["tsdf"]["merge"] joins a run's volume with an earlier run's saved one
+(tsdf_merge.py; tests/tsdf_merge_restatement.py).
+
 tsdf_live.py keeps such a volume during a run, while the poses still move; it fuses through
 `keyframe_observations`, the rule `fuse_keyframes` applies per chunk.
 """
@@ -43,6 +48,7 @@ from . import _lib
 from . import frontier as _frontier
 from . import localize as _localize
 from . import plan as _plan
+from . import tsdf_merge as _merge
 from . import view as _view
 from .lietorch_shim import SE3
 from .neus.mesh import Mesh, marching_cubes
@@ -251,6 +257,21 @@ class TSDFVolume:
         """How well do these poses explain the depth images?  One gs_tsdf_align_system per pose and no step ->
         {"rmse_m", "inlier_fraction", "count"} (`localize.pose_scores`)."""
         return _localize.pose_scores(self, depth, c2w, intrinsics, frame, stride, huber, max_depth, min_weight)
+
+    def register(self, other, T_init, levels=_merge.DEFAULT_LEVELS, huber=0.5, min_weight=1.0, lam_rel=1e-6, lam_abs=1e-9,
+                 min_count=64):
+        """Where does the volume `other` sit in this one?  B transforms other's world to this volume's world refined by
+        direct alignment of the two lattices (gs_tsdf_register_system / gs_tsdf_align_step), coarse to fine over `levels`
+        = (lattice stride, iterations) pairs: see `tsdf_merge.register_volumes` for the arguments and the returned dict
+        (T, ok, rmse_m, overlap, count, trace, moved_m, moved_deg, moved_constrained_m, n_constrained; host arrays, one
+        read)."""
+        return _merge.register_volumes(self, other, T_init, levels, huber, min_weight, lam_rel, lam_abs, min_count)
+
+    def merge(self, other, T=None, min_weight=1.0):
+        """Fuse the volume `other` into this one in place (gs_tsdf_merge) at the transform T, other's world to this
+        volume's ([3,4] / [4,4]; None: the identity): see `tsdf_merge.merge_volume`.  Drops the brick flags and returns
+        self."""
+        return _merge.merge_volume(self, other, T, min_weight)
 
     def save(self, path):
         """Write the volume as one .npz (tsdf, weight, colors, lo, voxel, trunc, max_weight, dims); `load` gives the same
@@ -919,11 +940,30 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
     batches) into {output}/metrics_tsdf_align.txt (localize.align_text; `tsdf_align_moved_mean_m`,
     `tsdf_align_moved_max_m`, `tsdf_align_moved_constrained_mean_m` -- the movement along the directions the surfaces in
     view constrain, localize.constrained_movement -- and `tsdf_align_failed` in `stats`); another mode, or a missing
-    stream, is refused before anything is fused or written.  Returns the Mesh, or None when the key is absent or
+    stream, is refused before anything is fused or written.  With cfg["tsdf"]["merge"] = {enable, volume, init, register,
+    levels, huber, min_count, save_volume} (absent by default) the volume an earlier run saved at `volume` is loaded, this
+    run's volume is registered to it from `init` (a 4 x 4 list, this run's world to the earlier run's; absent: the
+    identity; register false takes it as it is) and both are merged into a union volume (tsdf_merge.join_volumes) in the
+    earlier run's world: {output}/mesh/tsdf_merged_mesh.ply, {output}/metrics_tsdf_merge.txt (tsdf_merge.merge_text;
+    `tsdf_merge_overlap`, `tsdf_merge_rmse_m`, `tsdf_merge_moved_m` and `tsdf_merge_ok` in `stats`) and, with save_volume,
+    {output}/mesh/tsdf_merged_volume.npz.  A missing or unreadable file or a bad `init` is refused before anything is
+    fused, a failed registration before anything is written.  Returns the Mesh, or None when the key is absent or
     disabled."""
     opt = slam.cfg.get("tsdf") or {}
     if not opt.get("enable", False):
         return None
+    mg = opt.get("merge") or {}
+    earlier = None
+    if mg.get("enable", False):                             # refused before anything is fused or written
+        path = mg.get("volume")
+        if not path or not os.path.isfile(path):
+            raise ValueError(f"fuse_from_config: tsdf.merge.volume {path!r} is no file (TSDFVolume.save writes one)")
+        try:
+            earlier = TSDFVolume.load(path, device="cpu")
+        except Exception as e:
+            raise ValueError(f"fuse_from_config: tsdf.merge.volume {path!r} cannot be read as a saved volume: {e}") from None
+        merge_init = _merge.transforms34(np.eye(4) if mg.get("init") is None else np.asarray(mg["init"], np.float64),
+                                         "fuse_from_config: tsdf.merge.init")
     al = opt.get("align") or {}
     if al.get("enable", False):                             # refused before anything is fused or written
         if slam.cfg.get("mode", "rgbd") != "rgbd":
@@ -935,6 +975,14 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
     min_weight = float(opt.get("min_weight", 1.0))
     vol, mesh = fuse_keyframes(slam.video, bound, float(opt.get("voxel_size", 0.05)), source=opt.get("source", "tracked"),
                                trunc=opt.get("truncation"), min_weight=min_weight)
+    merged = None
+    if earlier is not None:                                 # a failed registration is refused before anything is written
+        for name in ("tsdf", "weight", "colors"):
+            setattr(earlier, name, getattr(earlier, name).to(vol.device))
+        earlier.device = vol.device
+        merged = _merge.join_volumes([earlier, vol], [None, merge_init[0]], register=mg.get("register", True),
+                                     min_weight=min_weight, levels=mg.get("levels", _merge.DEFAULT_LEVELS),
+                                     huber=mg.get("huber", 0.5), min_count=mg.get("min_count", 64))
     os.makedirs(f"{slam.output}/mesh", exist_ok=True)
     mesh.export(f"{slam.output}/mesh/tsdf_mesh.ply")
     ev = opt.get("eval_depth") or {}
@@ -1034,6 +1082,18 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
                   f"{res['n_candidates']} candidates, {res['n_qualified']} qualified")
     if opt.get("save_volume", False):
         vol.save(f"{slam.output}/mesh/tsdf_volume.npz")
+    if merged is not None:
+        joined, transforms, reports = merged
+        joined.extract_mesh(min_weight).export(f"{slam.output}/mesh/tsdf_merged_mesh.ply")
+        res = _merge.merge_report(reports[1])
+        with open(f"{slam.output}/metrics_tsdf_merge.txt", "w") as fh:
+            fh.write(_merge.merge_text(res, transforms[1]))
+        if mg.get("save_volume", False):
+            joined.save(f"{slam.output}/mesh/tsdf_merged_volume.npz")
+        if stats is not None:
+            stats.update(tsdf_merge_overlap=res["overlap"], tsdf_merge_rmse_m=res["rmse_m"],
+                         tsdf_merge_moved_m=res["moved_m"], tsdf_merge_ok=bool(res["ok"]))
+        print("TSDF merge: " + ", ".join(f"{k} {res[k]!r}" for k in _merge.MERGE_REPORT_ORDER))
     if al.get("enable", False):
         res = _localize.align_stream(vol, stream, c2w_list, (slam.video.intrinsics[0] * 8).cpu().tolist(),
                                      every=al.get("every", 5), out_path=f"{slam.output}/metrics_tsdf_align.txt",

@@ -430,6 +430,76 @@ int gs_tsdf_align_system(const float* tsdf, const float* weight, int nx, int ny,
 int gs_tsdf_align_step(const double* out, double* pose, int n_poses, double lam_rel, double lam_abs, int min_count,
                        double* trace, gs_stream_t stream);
 
+/* ---- two of those TSDF lattices put together: the Gauss-Newton system of a source volume S against a destination
+ *      volume D, and S resampled and fused into D (no counterpart in the reference), csrc/tsdf_merge.hip;
+ *      tests/tsdf_merge_restatement.py restates it ----
+ *
+ * A volume is tsdf, weight f32 [nx,ny,nz] (colors f32 [3,nx,ny,nz]) as above with its lo, voxel and trunc(ation); the
+ * suffixes _d and _s name D's and S's.  All fp32 and all fp64 arithmetic below is one rounding per operation, no fma;
+ * / is correctly rounded.  Sizes outside [2, 1024], stride < 1, n_poses < 0, a voxel or trunc that is not positive and
+ * finite, a lo that is not finite, huber <= 0, a NaN min_weight or a NULL pointer return GS_ERR_INVALID_ARG before
+ * anything is launched or written.
+ *
+ * gs_tsdf_register_workspace_bytes: n_poses * ceil(N / chunk) * 32 * 8 with chunk = gs_tsdf_align_chunk and N =
+ *   ceil(nx_s / stride) * ceil(ny_s / stride) * ceil(nz_s / stride), the chunks' partial rows; 0 for n_poses < 0, a
+ *   size outside [2, 1024], stride < 1 or more than 2^31 - 1 rows.  Needs no GPU.
+ * gs_tsdf_register_system: pose f64 [n_poses,3,4] on the device maps S-world to D-world, rows (r0 r1 r2 o); a batch of
+ *   hypotheses shares one launch.  workspace of at least gs_tsdf_register_workspace_bytes, out f64 [n_poses,32]; every
+ *   element of out is written; n_poses == 0 launches nothing.  The samples are S's lattice points (i, j, k) with every
+ *   index a multiple of stride, sample s = ((i / stride) * ceil(ny_s / stride) + j / stride) * ceil(nz_s / stride) +
+ *   k / stride.  ratio = trunc_s / trunc_d (one fp32 division).  Per pose (R, o) = (float) of each fp64 entry, and per
+ *   sample:
+ *
+ *     w = weight_s[i,j,k] ; fs = tsdf_s[i,j,k] ; fr = fs * ratio              (S's value in units of D's truncation)
+ *     the sample is considered iff w >= min_weight and fabsf(fs) < 1.0f and fabsf(fr) < 1.0f ; considered += 1 ; else skip
+ *     p  = lo_s + float(idx) * voxel_s                                        (per axis)
+ *     q  = (r0 * p.x + r1 * p.y) + r2 * p.z per row of R ; pw = q + o
+ *     g  = (pw - lo_d) / voxel_d ; a = floorf(g) ; skip unless 0 <= a < float(n_d - 1) on every axis and weight_d >=
+ *          min_weight at all eight corners a + {0,1}^3 ; fr' = g - a
+ *     f  = trilinear tsdf_d and n = its gradient, exactly gs_tsdf_align_system's sequences
+ *     skip unless fabsf(f) < 1.0f
+ *     r  = f - fr                                                             (the residual, in units of D's truncation)
+ *     gw = n / voxel_d per component
+ *     J  = (gw.x, gw.y, gw.z, q.y * gw.z - q.z * gw.y, q.z * gw.x - q.x * gw.z, q.x * gw.y - q.y * gw.x)
+ *     wt = fabsf(r) <= huber ? 1.0f : huber / fabsf(r)
+ *     in fp64: wj_i = (double)wt * (double)J_i ; H_ij += wj_i * (double)J_j for i <= j ; b_i += wj_i * (double)r ;
+ *              cost += ((double)wt * (double)r) * (double)r ; sq += (double)r * (double)r ; count += 1
+ *
+ *   out[b] has gs_tsdf_align_system's layout (H 21, b 6, cost 27, count 28, sq 29, considered 30, 0 at 31) and its
+ *   order of every fp64 sum: chunks of gs_tsdf_align_chunk samples, thread t of 256 adds its samples t, t + 256, ... in
+ *   increasing order onto 0.0, the wave's butterfly, the four waves as ((w0 + w1) + w2) + w3, the chunks' totals in
+ *   increasing order.  No atomics: two runs agree bitwise.  The rows are gs_tsdf_align_step's input: the step moves the
+ *   pose S-world to D-world by o' = o + v, R' = dR R.
+ * gs_tsdf_merge: S fused into D in place.  d2s f32 [3,4] ON THE HOST (read before the call returns) maps D-world to
+ *   S-world, rows (r0 r1 r2 t), finite.  trunc_s >= trunc_d (a source that saturates earlier would write "0.8 of the
+ *   truncation" where it only knows "free"), max_weight >= 1, min_weight > 0 (a cell no frame saw has nothing to add),
+ *   S and D distinct lattices; else GS_ERR_INVALID_ARG.  colors_d, colors_s: only when both are given are colours read
+ *   and written.  ratio = trunc_s / trunc_d.  Per lattice point (i,j,k) of D, in fp32:
+ *
+ *     p  = lo_d + float(idx) * voxel_d                                        (per axis)
+ *     ps = ((r0 * p.x + r1 * p.y) + r2 * p.z) + t                             (per row of d2s)
+ *     g  = (ps - lo_s) / voxel_s ; a = floorf(g) ; skip unless 0 <= a < float(n_s - 1) on every axis (a NaN fails)
+ *     skip unless weight_s >= min_weight at all eight corners a + {0,1}^3 ; fr = g - a
+ *     fs = trilinear tsdf_s, ws = trilinear weight_s, cs = trilinear colors_s per channel: lerp(p, q, s) = p + s *
+ *          (q - p) along z (four), then y (two), then x (one)
+ *     s  = fs * ratio ; skip if s < -1.0f ; s = fminf(1.0f, s)
+ *     w0 = weight_d ; w1 = w0 + ws
+ *     tsdf_d   = (tsdf_d * w0 + s * ws) / w1
+ *     colors_d = (colors_d * w0 + cs * ws) / w1                               (per channel, with colours)
+ *     weight_d = fminf(w1, max_weight)
+ *
+ *   A skipped point keeps its bits.  One lane owns a point: no atomics, results independent of the launch geometry.  */
+size_t gs_tsdf_register_workspace_bytes(int n_poses, int nx_s, int ny_s, int nz_s, int stride);
+int gs_tsdf_register_system(const float* tsdf_d, const float* weight_d, int nx_d, int ny_d, int nz_d, float lo_dx,
+                            float lo_dy, float lo_dz, float voxel_d, float trunc_d, const float* tsdf_s,
+                            const float* weight_s, int nx_s, int ny_s, int nz_s, float lo_sx, float lo_sy, float lo_sz,
+                            float voxel_s, float trunc_s, const double* pose, int n_poses, int stride, float min_weight,
+                            float huber, void* workspace, double* out, gs_stream_t stream);
+int gs_tsdf_merge(float* tsdf_d, float* weight_d, float* colors_d, int nx_d, int ny_d, int nz_d, float lo_dx, float lo_dy,
+                  float lo_dz, float voxel_d, float trunc_d, float max_weight, const float* tsdf_s, const float* weight_s,
+                  const float* colors_s, int nx_s, int ny_s, int nz_s, float lo_sx, float lo_sy, float lo_sz,
+                  float voxel_s, float trunc_s, const float* d2s, float min_weight, gs_stream_t stream);
+
 /* ---- Euclidean distance field and 2-D occupancy map of that TSDF lattice (no counterpart in the reference),
  *      csrc/esdf.hip; tests/esdf_restatement.py restates it serially ----
  *
