@@ -74,6 +74,8 @@ static inline size_t gs_align(size_t x, size_t a = 256) { return (x + a - 1) / a
 __device__ __forceinline__ float gs_clamp_keep_nan(float v, float lo, float hi) {
   return v < lo ? lo : (v > hi ? hi : v);
 }
+// torch's relu: a NaN stays a NaN (fmaxf(v, 0) alone would turn it into 0); every other value as fmaxf gives it
+__device__ __forceinline__ float gs_relu_keep_nan(float v) { return v != v ? v : fmaxf(v, 0.0f); }
 
 // ---------------------------------------------------------------- SE3 on the device ----
 // Pose layout [tx,ty,tz,qx,qy,qz,qw] (world->camera), see SURVEY App. A.  All of these are

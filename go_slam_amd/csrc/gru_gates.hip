@@ -128,7 +128,7 @@ __global__ __launch_bounds__(256) void bias_act_kernel(const _Float16* __restric
     for (int k = 0; k < 8; ++k) {
       float f = (float)v[k];
       if (BIAS) f += bias[c8 * 8 + k];
-      if (ACT == 1) f = fmaxf(f, 0.0f);
+      if (ACT == 1) f = gs_relu_keep_nan(f);
       if (ACT == 2) f = sigm(f);
       v[k] = (_Float16)f;
     }
@@ -168,7 +168,7 @@ __global__ __launch_bounds__(256) void segment_mean_kernel(const _Float16* __res
         float f = (float)v[u][j];
         if (touch) {
           f += bias[j];
-          if (in_relu) f = fmaxf(f, 0.0f);
+          if (in_relu) f = gs_relu_keep_nan(f);
           f = (float)(_Float16)f;              // the activation the reference materialises in fp16
         }
         acc[j] += f;
@@ -178,7 +178,14 @@ __global__ __launch_bounds__(256) void segment_mean_kernel(const _Float16* __res
   const float inv = e > b ? 1.0f / (float)(e - b) : 0.0f;
   half8 o;
 #pragma unroll
-  for (int j = 0; j < 8; ++j) o[j] = (_Float16)(acc[j] * inv);
+  for (int j = 0; j < 8; ++j) {
+    // the fp32 product is pinned to a register: left alone, the compiler folds product + conversion of channels 0 and 7
+    // of the eight into v_fma_mixlo/hi_f16 (ONE rounding of the exact product) and keeps v_pk_mul_f32 + v_cvt for the
+    // other six -- where sum / count lies exactly between two fp16 values the channels then rounded differently
+    float m = acc[j] * inv;
+    asm volatile("" : "+v"(m));
+    o[j] = (_Float16)m;
+  }
   reinterpret_cast<half8*>(out)[t] = o;
 }
 

@@ -133,12 +133,14 @@ __global__ __launch_bounds__(512, 1) void upmask_upsample_kernel(const _Float16*
   const long gstride = (long)gridDim.x * 32;
   up_h8 bnext[8];
   long fnext;                                        // the frame of the next block's pixel: requested with its rows
-  const int64_t* ixp = ix ? ix : reinterpret_cast<const int64_t*>(disps);   // (no index list: any readable words, unused)
+  // (no index list: readable words, unused -- word 0 of x, whose rows hold >= 256 bytes; disps has only 4 m h w bytes,
+  // fewer than m words on a 1 x 1 map)
+  const int64_t* ixp = ix ? ix : reinterpret_cast<const int64_t*>(x);
   {
     const long g0 = (long)blockIdx.x * 32;
     const long pq0 = (g0 + r < total) ? g0 + r : (g0 < total ? g0 : 0);
     const int n0 = (int)(pq0 / hw);
-    { const long f = ixp[n0]; fnext = ix ? f : (long)n0; }
+    { const long f = ixp[ix ? n0 : 0]; fnext = ix ? f : (long)n0; }
     const _Float16* xr0 = x + (size_t)pq0 * xs + 8 * kgl;
 #pragma unroll
     for (int s = 0; s < 8; ++s) bnext[s] = *reinterpret_cast<const up_h8*>(xr0 + 16 * s);
@@ -156,7 +158,7 @@ __global__ __launch_bounds__(512, 1) void upmask_upsample_kernel(const _Float16*
       const long g1 = g0 + gstride;
       const long pq1 = (g1 + r < total) ? g1 + r : (g1 < total ? g1 : pq);
       const int n1 = (int)(pq1 / hw);
-      { const long f = ixp[n1]; fnext = ix ? f : (long)n1; }
+      { const long f = ixp[ix ? n1 : 0]; fnext = ix ? f : (long)n1; }
       const _Float16* xr1 = x + (size_t)pq1 * xs + 8 * kgl;
 #pragma unroll
       for (int s = 0; s < 8; ++s) bnext[s] = *reinterpret_cast<const up_h8*>(xr1 + 16 * s);

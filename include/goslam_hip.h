@@ -734,7 +734,8 @@ int gs_gru_gate_q(const void* q_pre, const float* bias_q, const float* glo_q, co
 /* y[row, 0:channels] = act(x[row, 0:channels] + bias) for NHWC fp16 data viewed as [rows, channels]
  * (channels % 8 == 0); x / y rows are x_stride / y_stride elements apart, so y may be x itself (in
  * place) and either side may be a channel slice of a wider NHWC tensor (replaces torch.cat / split).  bias may be
- * NULL (plain strided copy when act == 0).  act: 0 none, 1 ReLU, 2 sigmoid.
+ * NULL (plain strided copy when act == 0).  act: 0 none, 1 ReLU (a NaN stays a NaN, as torch.relu), 2 sigmoid.
+ * fp32 arithmetic, one rounding to fp16: y = half(act(float(x) + bias)).
  * Epilogue of the bias-free MIOpen convolutions of src/droid_net.py:69-140.                       */
 int gs_bias_act(const void* x, const float* bias, void* y, int rows, int channels, int x_stride, int y_stride,
                 int act, gs_stream_t stream);
@@ -848,7 +849,10 @@ int gs_conv3x3_heads_finish(const float* tap, const float* bias0, const float* b
  * out[s, p, :] = mean over k in [seg_offsets[s], seg_offsets[s+1]) of act(x[seg_edges[k], p, :]), NHWC
  * fp16 [*, hw, channels] (channels % 8 == 0, x rows x_stride elements apart), fp32 accumulation.
  * act = relu?(. + in_bias) rounded to fp16 when in_bias != NULL or in_relu (the producer
- * convolution's epilogue applied on the fly), identity otherwise.                                   */
+ * convolution's epilogue applied on the fly), identity otherwise; the ReLU keeps a NaN (torch.relu).  The fp32 sum
+ * runs over the segment's edges in seg_edges order, is multiplied by fp32(1 / count) and rounded once to fp16.
+ * seg_edges need not be sorted, may name an edge in several segments and may leave edges unused.  An empty
+ * segment (seg_offsets[s] == seg_offsets[s+1]) is written as zeros.                                  */
 int gs_segment_mean(const void* x, int x_stride, const float* in_bias, int in_relu, const int* seg_offsets,
                     const int* seg_edges, void* out, int n_seg, int hw, int channels, gs_stream_t stream);
 /* Frame encoders (src/modules/extractor.py:27-57 ResidualBlock.forward, :113-126 BasicEncoder.forward): the
@@ -891,7 +895,9 @@ int gs_norm_act(const void* x, const void* bias, const void* skip, void* y, int 
 /* ConvGRU global context (src/modules/gru.py:22-27): glo = mean_hw(sigmoid(w_pre + w_bias) * net),
  * then the three 1x1 convolutions convz_glo | convr_glo (-> gzr [n,256]) and convq_glo (-> gq [n,128]).
  * w_pre = bias-free 1x1 conv of net, NHWC fp16 [n,hw,128]; wz/wr/wq fp16 [128 out,128 in]; outputs f32
- * holding fp16-rounded values (what autocast produces).                                           */
+ * holding fp16-rounded values (what autocast produces).  Rounding points: g = half(sigmoid(half(w_pre + w_bias))),
+ * t = half(g * net), fp32 sum of t over the pixels (fixed order: deterministic) times fp32(1 / hw) rounded to fp16, then
+ * per head half(b + sum_k W[o][k] glo[k]) with fp32 accumulation starting from the bias.              */
 size_t gs_gru_glo_workspace_bytes(int n);
 int gs_gru_glo(const void* w_pre, const float* w_bias, const void* net, const void* wz, const void* wr,
                const void* wq, const float* bz, const float* br, const float* bq, float* gzr, float* gq,
