@@ -14,13 +14,14 @@
 // Every pass is the header's early-exit loop: bounded by R <= 1023 whatever the data holds.  `dist` is the int32
 // ping-pong buffer (z -> d2, y -> dist, x -> d2, finish -> dist).  No atomics, no scratch; every point, query and map
 // column is owned by one lane, so nothing depends on the launch geometry.
-#include "common.h"
+#include "tsdf_cell.h"
 
 namespace {
 
 constexpr int ESDF_THREADS = 256;
 constexpr int ESDF_WAVES = ESDF_THREADS / 64;
-constexpr int ESDF_MAX = 1024;              // lattice points per axis
+constexpr int ESDF_MAX = 1024;              // lattice points per axis: sizes the LDS lines of esdf_sites_z_kernel
+static_assert(ESDF_MAX == TSDF_DIM_MAX, "tsdf_dims_ok admits the lattices whose lines fit");
 constexpr int ESDF_INF = 0x3fffffff;
 constexpr int ESDF_FAR = 0x7fffffff;
 
@@ -120,8 +121,6 @@ __global__ __launch_bounds__(ESDF_THREADS) void esdf_finish_kernel(const int* __
   dist[p] = state[p] == 2 ? -d : d;
 }
 
-__device__ __forceinline__ float esdf_lerp(float p, float q, float s) { return p + s * (q - p); }
-
 __global__ __launch_bounds__(ESDF_THREADS) void esdf_query_kernel(
     const float* __restrict__ dist, const unsigned char* __restrict__ state, int nx, int ny, int nz, float lox, float loy,
     float loz, float voxel, const float* __restrict__ points, int n, float* __restrict__ out_dist,
@@ -139,21 +138,14 @@ __global__ __launch_bounds__(ESDF_THREADS) void esdf_query_kernel(
     const size_t at = ((size_t)(int)ax * ny + (int)ay) * nz + (int)az;
     const size_t sy = (size_t)nz, sx = (size_t)ny * nz;
     const float fx = gx - ax, fy = gy - ay, fz = gz - az;
-    const float v000 = dist[at], v001 = dist[at + 1], v010 = dist[at + sy], v011 = dist[at + sy + 1];
-    const float v100 = dist[at + sx], v101 = dist[at + sx + 1], v110 = dist[at + sx + sy], v111 = dist[at + sx + sy + 1];
+    const TsdfCorners c = tsdf_corners_load(dist, at, ny, nz);
     const bool known = state[at] != 0 && state[at + 1] != 0 && state[at + sy] != 0 && state[at + sy + 1] != 0 &&
                        state[at + sx] != 0 && state[at + sx + 1] != 0 && state[at + sx + sy] != 0 &&
                        state[at + sx + sy + 1] != 0;
-    // z-lerps of the four z edges, y-lerps of the four y edges
-    const float z00 = esdf_lerp(v000, v001, fz), z01 = esdf_lerp(v010, v011, fz);
-    const float z10 = esdf_lerp(v100, v101, fz), z11 = esdf_lerp(v110, v111, fz);
-    const float y00 = esdf_lerp(v000, v010, fy), y01 = esdf_lerp(v001, v011, fy);
-    const float y10 = esdf_lerp(v100, v110, fy), y11 = esdf_lerp(v101, v111, fy);
-    const float x0 = esdf_lerp(z00, z01, fy), x1 = esdf_lerp(z10, z11, fy);
-    d = esdf_lerp(x0, x1, fx);
-    g0 = (x1 - x0) / voxel;
-    g1 = (esdf_lerp(z01, z11, fx) - esdf_lerp(z00, z10, fx)) / voxel;
-    g2 = (esdf_lerp(y01, y11, fx) - esdf_lerp(y00, y10, fx)) / voxel;
+    float g[3];
+    d = tsdf_corners_value(c, fx, fy, fz);
+    tsdf_corners_gradient(c, fx, fy, fz, g);
+    g0 = g[0] / voxel; g1 = g[1] / voxel; g2 = g[2] / voxel;
     flags = known ? 3 : 1;
   }
   out_dist[p] = d;
@@ -187,15 +179,11 @@ __global__ __launch_bounds__(ESDF_THREADS) void esdf_slice_kernel(
   clearance[p] = c;
 }
 
-bool esdf_dims_ok(int nx, int ny, int nz) {
-  return nx >= 2 && nx <= ESDF_MAX && ny >= 2 && ny <= ESDF_MAX && nz >= 2 && nz <= ESDF_MAX;
-}
-
 }  // namespace
 
 extern "C" int gs_esdf_build(const float* tsdf, const float* weight, int nx, int ny, int nz, float min_weight,
                              int radius, float voxel, unsigned char* state, int* d2, float* dist, gs_stream_t stream) {
-  GS_REQUIRE(esdf_dims_ok(nx, ny, nz), "esdf_build: lattice %d x %d x %d outside [2, 1024]", nx, ny, nz);
+  GS_REQUIRE(tsdf_dims_ok(nx, ny, nz), "esdf_build: lattice %d x %d x %d outside [2, 1024]", nx, ny, nz);
   GS_REQUIRE(radius >= 1 && radius <= ESDF_MAX - 1, "esdf_build: radius %d outside [1, 1023] voxels", radius);
   GS_REQUIRE(voxel > 0.0f && voxel < INFINITY, "esdf_build: voxel=%g", voxel);
   GS_REQUIRE(min_weight == min_weight, "esdf_build: min_weight is NaN");
@@ -222,7 +210,7 @@ extern "C" int gs_esdf_build(const float* tsdf, const float* weight, int nx, int
 extern "C" int gs_esdf_query(const float* dist, const unsigned char* state, int nx, int ny, int nz, float lo_x,
                              float lo_y, float lo_z, float voxel, const float* points, int n, float* out_dist,
                              float* out_grad, unsigned char* out_flags, gs_stream_t stream) {
-  GS_REQUIRE(esdf_dims_ok(nx, ny, nz), "esdf_query: lattice %d x %d x %d outside [2, 1024]", nx, ny, nz);
+  GS_REQUIRE(tsdf_dims_ok(nx, ny, nz), "esdf_query: lattice %d x %d x %d outside [2, 1024]", nx, ny, nz);
   GS_REQUIRE(voxel > 0.0f && voxel < INFINITY, "esdf_query: voxel=%g", voxel);
   GS_REQUIRE(n >= 0, "esdf_query: n=%d", n);
   if (n == 0) return GS_OK;
@@ -237,7 +225,7 @@ extern "C" int gs_esdf_query(const float* dist, const unsigned char* state, int 
 extern "C" int gs_esdf_slice(const unsigned char* state, const int* d2, const float* dist, int nx, int ny, int nz,
                              int up_axis, int k0, int k1, int occ_d2, int min_known, unsigned char* cells,
                              float* clearance, gs_stream_t stream) {
-  GS_REQUIRE(esdf_dims_ok(nx, ny, nz), "esdf_slice: lattice %d x %d x %d outside [2, 1024]", nx, ny, nz);
+  GS_REQUIRE(tsdf_dims_ok(nx, ny, nz), "esdf_slice: lattice %d x %d x %d outside [2, 1024]", nx, ny, nz);
   GS_REQUIRE(up_axis >= 0 && up_axis <= 2, "esdf_slice: up_axis=%d outside 0..2", up_axis);
   const int n[3] = {nx, ny, nz};
   const long long stride[3] = {(long long)ny * nz, (long long)nz, 1};

@@ -11,7 +11,7 @@
 // 64-point run spans and keeps a bit per frame; frames without a bit are not evaluated, and a wave without any bit
 // neither loads nor stores.  See tsdf_run_may_hit for why the test cannot change a result.
 #pragma once
-#include "common.h"
+#include "tsdf_cell.h"      // tsdf_dims_ok
 
 namespace {
 
@@ -118,10 +118,6 @@ __device__ __forceinline__ void tsdf_fuse(const Rule rule, const TsdfSweep sw) {
     rule.fold(state, f, s, COLOR && sdf <= trunc ? sw.images + (size_t)f * 3 * hw + (pix - (size_t)f * hw) : nullptr, hw);
   }
   rule.store(state, at, (size_t)sw.npoints, COLOR);
-}
-
-bool tsdf_dims_ok(int nx, int ny, int nz) {
-  return nx >= 2 && nx <= 1024 && ny >= 2 && ny <= 1024 && nz >= 2 && nz <= 1024;
 }
 
 // |(fx, 0, a)| in double, rounded up to float: a larger norm only widens the skip test's margin

@@ -11,7 +11,7 @@
 // before a candidate far end is evaluated on demand (see the header for why this cannot change a result).
 //
 // tsdf_brick_flags_kernel: one wave per brick; lanes stride over the brick's up to 9^3 corner points, the wave votes.
-#include "common.h"
+#include "tsdf_cell.h"
 
 namespace {
 
@@ -20,10 +20,9 @@ constexpr int RAY_THREADS = RAY_TILE * RAY_TILE;
 constexpr int BRICK = 8;                    // cells per side of a brick
 
 struct RayVol {            // by-value kernel arguments (SGPRs)
-  int nx, ny, nz;
+  TsdfLattice l;
+  int nx;
   int by, bz;              // bricks along y and z
-  float topx, topy, topz;  // float(n - 1)
-  float lox, loy, loz, voxel;
   float min_weight;
 };
 
@@ -33,47 +32,21 @@ struct RayCell {
   int ax, ay, az;
 };
 
-// the cell of g: false unless 0 <= floorf(g) < n - 1 on every axis (NaN fails), compared before the casts
+// the cell of g: false unless g has one (tsdf_cell_inside)
 __device__ __forceinline__ bool ray_cell(const RayVol v, float gx, float gy, float gz, RayCell& c) {
   const float ax = floorf(gx), ay = floorf(gy), az = floorf(gz);
-  if (!(ax >= 0.0f && ax < v.topx && ay >= 0.0f && ay < v.topy && az >= 0.0f && az < v.topz)) return false;
+  if (!tsdf_cell_inside(v.l, ax, ay, az)) return false;
   c.ax = (int)ax; c.ay = (int)ay; c.az = (int)az;
-  c.at = ((size_t)c.ax * v.ny + c.ay) * v.nz + c.az;
+  c.at = tsdf_cell_at<size_t>(v.l, c.ax, c.ay, c.az);
   c.sx = gx - ax; c.sy = gy - ay; c.sz = gz - az;
   return true;
-}
-
-__device__ __forceinline__ float ray_lerp(float p, float q, float s) { return p + s * (q - p); }
-
-struct RayCorners { float v000, v001, v010, v011, v100, v101, v110, v111; };   // v[x][y][z]
-
-__device__ __forceinline__ RayCorners ray_load(const float* __restrict__ p, size_t at, int ny, int nz) {
-  const size_t sy = (size_t)nz, sx = (size_t)ny * nz;
-  RayCorners c;
-  c.v000 = p[at];           c.v001 = p[at + 1];
-  c.v010 = p[at + sy];      c.v011 = p[at + sy + 1];
-  c.v100 = p[at + sx];      c.v101 = p[at + sx + 1];
-  c.v110 = p[at + sx + sy]; c.v111 = p[at + sx + sy + 1];
-  return c;
-}
-
-__device__ __forceinline__ bool ray_seen(const RayCorners w, float m) {
-  return w.v000 >= m && w.v001 >= m && w.v010 >= m && w.v011 >= m && w.v100 >= m && w.v101 >= m && w.v110 >= m &&
-         w.v111 >= m;
-}
-
-// lerps along z (four), then y (two), then x (one)
-__device__ __forceinline__ float ray_trilinear(const RayCorners c, float sx, float sy, float sz) {
-  const float c00 = ray_lerp(c.v000, c.v001, sz), c01 = ray_lerp(c.v010, c.v011, sz);
-  const float c10 = ray_lerp(c.v100, c.v101, sz), c11 = ray_lerp(c.v110, c.v111, sz);
-  return ray_lerp(ray_lerp(c00, c01, sy), ray_lerp(c10, c11, sy), sx);
 }
 
 // sample(t) of the header: valid?, and the value
 __device__ __forceinline__ bool ray_sample(const float* __restrict__ tsdf, const float* __restrict__ weight,
                                            const RayVol v, const RayCell c, float& f) {
-  if (!ray_seen(ray_load(weight, c.at, v.ny, v.nz), v.min_weight)) return false;
-  f = ray_trilinear(ray_load(tsdf, c.at, v.ny, v.nz), c.sx, c.sy, c.sz);
+  if (!tsdf_corners_at_least(tsdf_corners_load(weight, c.at, v.l.ny, v.l.nz), v.min_weight)) return false;
+  f = tsdf_corners_value(tsdf_corners_load(tsdf, c.at, v.l.ny, v.l.nz), c.sx, c.sy, c.sz);
   return true;
 }
 
@@ -100,17 +73,17 @@ __global__ __launch_bounds__(RAY_THREADS) void tsdf_raycast_kernel(
     const float dwx = (m[0] * dx + m[1] * dy) + m[2];
     const float dwy = (m[4] * dx + m[5] * dy) + m[6];
     const float dwz = (m[8] * dx + m[9] * dy) + m[10];
-    const float ogx = (m[3] - v.lox) / v.voxel, ogy = (m[7] - v.loy) / v.voxel, ogz = (m[11] - v.loz) / v.voxel;
-    const float dgx = dwx / v.voxel, dgy = dwy / v.voxel, dgz = dwz / v.voxel;
+    const float ogx = (m[3] - v.l.lox) / v.l.voxel, ogy = (m[7] - v.l.loy) / v.l.voxel, ogz = (m[11] - v.l.loz) / v.l.voxel;
+    const float dgx = dwx / v.l.voxel, dgy = dwy / v.l.voxel, dgz = dwz / v.l.voxel;
     if (!(ray_finite(ogx) && ray_finite(ogy) && ray_finite(ogz) && ray_finite(dgx) && ray_finite(dgy) &&
           ray_finite(dgz)))
       break;
-    const float dt = (step * v.voxel) / sqrtf((dwx * dwx + dwy * dwy) + dwz * dwz);
+    const float dt = (step * v.l.voxel) / sqrtf((dwx * dwx + dwy * dwy) + dwz * dwz);
     if (!(dt > 0.0f && dt < INFINITY)) break;
     float t0 = near, t1 = far;
     bool inside = true;
     {
-      const float og[3] = {ogx, ogy, ogz}, dg[3] = {dgx, dgy, dgz}, top[3] = {v.topx, v.topy, v.topz};
+      const float og[3] = {ogx, ogy, ogz}, dg[3] = {dgx, dgy, dgz}, top[3] = {v.l.topx, v.l.topy, v.l.topz};
 #pragma unroll
       for (int a = 0; a < 3; ++a) {
         if (dg[a] == 0.0f) {
@@ -162,26 +135,19 @@ __global__ __launch_bounds__(RAY_THREADS) void tsdf_raycast_kernel(
 
     RayCell c;
     if (!ray_cell(v, ogx + t_star * dgx, ogy + t_star * dgy, ogz + t_star * dgz, c)) break;
-    if (!ray_seen(ray_load(weight, c.at, v.ny, v.nz), v.min_weight)) break;
-    const RayCorners s = ray_load(tsdf, c.at, v.ny, v.nz);
-    // z-lerps of the four z-edges, y-lerps of the four y-edges
-    const float z00 = ray_lerp(s.v000, s.v001, c.sz), z01 = ray_lerp(s.v010, s.v011, c.sz);
-    const float z10 = ray_lerp(s.v100, s.v101, c.sz), z11 = ray_lerp(s.v110, s.v111, c.sz);
-    const float y00 = ray_lerp(s.v000, s.v010, c.sy), y01 = ray_lerp(s.v001, s.v011, c.sy);
-    const float y10 = ray_lerp(s.v100, s.v110, c.sy), y11 = ray_lerp(s.v101, s.v111, c.sy);
-    const float nx = ray_lerp(z10, z11, c.sy) - ray_lerp(z00, z01, c.sy);
-    const float ny = ray_lerp(z01, z11, c.sx) - ray_lerp(z00, z10, c.sx);
-    const float nz = ray_lerp(y01, y11, c.sx) - ray_lerp(y00, y10, c.sx);
-    const float len = sqrtf((nx * nx + ny * ny) + nz * nz);
+    if (!tsdf_corners_at_least(tsdf_corners_load(weight, c.at, v.l.ny, v.l.nz), v.min_weight)) break;
+    float n[3];
+    tsdf_corners_gradient(tsdf_corners_load(tsdf, c.at, v.l.ny, v.l.nz), c.sx, c.sy, c.sz, n);
+    const float len = sqrtf((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
     out_d = t_star;
     if (len > 0.0f) {
-      out_n[0] = nx / len; out_n[1] = ny / len; out_n[2] = nz / len;
+      out_n[0] = n[0] / len; out_n[1] = n[1] / len; out_n[2] = n[2] / len;
     }
     if (COLOR) {
-      const size_t np = (size_t)v.nx * v.ny * v.nz;
+      const size_t np = (size_t)v.nx * v.l.ny * v.l.nz;
 #pragma unroll
       for (int ch = 0; ch < 3; ++ch)
-        out_c[ch] = ray_trilinear(ray_load(colors + ch * np, c.at, v.ny, v.nz), c.sx, c.sy, c.sz);
+        out_c[ch] = tsdf_corners_value(tsdf_corners_load(colors + ch * np, c.at, v.l.ny, v.l.nz), c.sx, c.sy, c.sz);
     }
   } while (false);
 
@@ -214,20 +180,16 @@ __global__ __launch_bounds__(64) void tsdf_brick_flags_kernel(const float* __res
   if (threadIdx.x == 0) flags[brick] = any ? 1 : 0;
 }
 
-bool ray_dims_ok(int nx, int ny, int nz) {
-  return nx >= 2 && nx <= 1024 && ny >= 2 && ny <= 1024 && nz >= 2 && nz <= 1024;
-}
-
 }  // namespace
 
 extern "C" size_t gs_tsdf_brick_flags_bytes(int nx, int ny, int nz) {
-  if (!ray_dims_ok(nx, ny, nz)) return 0;
+  if (!tsdf_dims_ok(nx, ny, nz)) return 0;
   return (size_t)gs_cdiv(nx - 1, BRICK) * gs_cdiv(ny - 1, BRICK) * gs_cdiv(nz - 1, BRICK);
 }
 
 extern "C" int gs_tsdf_brick_flags(const float* tsdf, int nx, int ny, int nz, unsigned char* flags,
                                    gs_stream_t stream) {
-  GS_REQUIRE(ray_dims_ok(nx, ny, nz), "tsdf_brick_flags: lattice %d x %d x %d outside [2, 1024]", nx, ny, nz);
+  GS_REQUIRE(tsdf_dims_ok(nx, ny, nz), "tsdf_brick_flags: lattice %d x %d x %d outside [2, 1024]", nx, ny, nz);
   GS_REQUIRE(tsdf && flags, "tsdf_brick_flags: null pointer");
   const int by = gs_cdiv(ny - 1, BRICK), bz = gs_cdiv(nz - 1, BRICK);
   const unsigned bricks = (unsigned)gs_tsdf_brick_flags_bytes(nx, ny, nz);      // at most 128^3
@@ -242,7 +204,7 @@ extern "C" int gs_tsdf_raycast(const float* tsdf, const float* weight, const flo
                                float cx, float cy, float lo_x, float lo_y, float lo_z, float voxel, float near,
                                float far, float step_voxels, float min_weight, float* depth, float* normal,
                                float* color, gs_stream_t stream) {
-  GS_REQUIRE(ray_dims_ok(nx, ny, nz), "tsdf_raycast: lattice %d x %d x %d outside [2, 1024]", nx, ny, nz);
+  GS_REQUIRE(tsdf_dims_ok(nx, ny, nz), "tsdf_raycast: lattice %d x %d x %d outside [2, 1024]", nx, ny, nz);
   GS_REQUIRE(k >= 0 && h >= 1 && w >= 1, "tsdf_raycast: k=%d h=%d w=%d", k, h, w);
   GS_REQUIRE(step_voxels > 0.0f && step_voxels <= 1.0f, "tsdf_raycast: step_voxels=%g outside (0, 1]", step_voxels);
   GS_REQUIRE(voxel > 0.0f && voxel < INFINITY, "tsdf_raycast: voxel=%g", voxel);
@@ -257,10 +219,9 @@ extern "C" int gs_tsdf_raycast(const float* tsdf, const float* weight, const flo
   const long long tiles = (long long)tiles_x * tiles_y, blocks = tiles * k;
   GS_REQUIRE(blocks <= 0x7fffffffLL, "tsdf_raycast: %d frames of %d x %d pixels are too many for one launch", k, h, w);
   RayVol v;
-  v.nx = nx; v.ny = ny; v.nz = nz;
+  v.l = tsdf_lattice(nx, ny, nz, lo_x, lo_y, lo_z, voxel);
+  v.nx = nx;
   v.by = gs_cdiv(ny - 1, BRICK); v.bz = gs_cdiv(nz - 1, BRICK);
-  v.topx = (float)(nx - 1); v.topy = (float)(ny - 1); v.topz = (float)(nz - 1);
-  v.lox = lo_x; v.loy = lo_y; v.loz = lo_z; v.voxel = voxel;
   v.min_weight = min_weight;
   GS_TIMING_PRE();
   if (color)

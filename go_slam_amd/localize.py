@@ -94,42 +94,89 @@ def _inputs(vol, what, depth, c2w, intrinsics, frame, huber, max_depth, min_weig
     return depth, poses, fr, intr, huber, max_depth, min_weight
 
 
+def _buffers(dev, poses, nbytes):
+    """(pose [B,3,4], rows [B,32], the chunks' workspace of `nbytes`): float64 on `dev`."""
+    B = int(poses.shape[0])
+    return (torch.from_numpy(poses).to(dev), torch.empty(B, 32, dtype=torch.float64, device=dev),
+            torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=dev))
+
+
 class _Systems:
-    """The device side of a batch of poses: pose [B,3,4], rows [B,32], the chunks' workspace; enqueues on the current
-    stream and reads nothing."""
+    """gs_tsdf_align_system for poses against depth maps.  The depth maps and the poses' frames go to the device at the
+    first `system`, which enqueues on the current stream and reads nothing."""
 
-    def __init__(self, vol, depth, poses, frame, intr, huber, max_depth, min_weight, min_stride, what):
+    def __init__(self, vol, depth, frame, intr, huber, max_depth, min_weight, what):
         self.vol, self.intr, self.what = vol, intr, what
-        self.depth = depth = depth.to(device=vol.device, dtype=torch.float32).contiguous()
+        self.depth, self.frame, self.on_device = depth, frame, None
         self.huber, self.max_depth, self.min_weight = huber, max_depth, min_weight
-        dev = vol.device
-        self.B = int(poses.shape[0])
-        self.pose = torch.from_numpy(poses).to(dev)
-        self.frame = torch.from_numpy(frame).to(dev)
-        self.rows = torch.empty(self.B, 32, dtype=torch.float64, device=dev)
-        k, H, W = depth.shape
-        nbytes = _lib.lib().gs_tsdf_align_workspace_bytes(self.B, H, W, min_stride)
-        if self.B and nbytes == 0:
-            raise ValueError(f"{what}: {self.B} poses of {H} x {W} pixels at stride {min_stride} are too many for one call")
-        self.workspace = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=dev)
 
-    def system(self, stride):
-        vol = self.vol
-        nx, ny, nz = vol.dims
+    def workspace_bytes(self, B, min_stride):
         k, H, W = self.depth.shape
+        nbytes = _lib.lib().gs_tsdf_align_workspace_bytes(B, H, W, min_stride)
+        if B and nbytes == 0:
+            raise ValueError(f"{self.what}: {B} poses of {H} x {W} pixels at stride {min_stride} are too many for one call")
+        return nbytes
+
+    def system(self, stride, pose, rows, workspace):
+        vol = self.vol
+        if self.on_device is None:
+            self.on_device = (self.depth.to(device=vol.device, dtype=torch.float32).contiguous(),
+                              torch.from_numpy(self.frame).to(vol.device))
+        depth, frame = self.on_device
+        nx, ny, nz = vol.dims
+        k, H, W = depth.shape
         with torch.cuda.device(vol.device):
             rc = _lib.lib().gs_tsdf_align_system(
-                _lib.ptr(vol.tsdf), _lib.ptr(vol.weight), nx, ny, nz, _lib.ptr(self.depth), _lib.ptr(self.frame),
-                _lib.ptr(self.pose), self.B, int(k), int(H), int(W), int(stride), *self.intr, float(vol.lo[0]),
-                float(vol.lo[1]), float(vol.lo[2]), vol.voxel, self.max_depth, self.min_weight, self.huber,
-                _lib.ptr(self.workspace), _lib.ptr(self.rows), _lib.stream_ptr(vol.device))
+                _lib.ptr(vol.tsdf), _lib.ptr(vol.weight), nx, ny, nz, _lib.ptr(depth), _lib.ptr(frame), _lib.ptr(pose),
+                int(pose.shape[0]), int(k), int(H), int(W), int(stride), *self.intr, float(vol.lo[0]), float(vol.lo[1]),
+                float(vol.lo[2]), vol.voxel, self.max_depth, self.min_weight, self.huber, _lib.ptr(workspace),
+                _lib.ptr(rows), _lib.stream_ptr(vol.device))
         _lib.check(rc, self.what)
 
-    def step(self, lam_rel, lam_abs, min_count, trace_row):
-        with torch.cuda.device(self.vol.device):
-            rc = _lib.lib().gs_tsdf_align_step(_lib.ptr(self.rows), _lib.ptr(self.pose), self.B, lam_rel, lam_abs,
-                                               min_count, _lib.ptr(trace_row), _lib.stream_ptr(self.vol.device))
-        _lib.check(rc, self.what)
+
+def gauss_newton(what, dev, poses, levels, trunc, lam_rel, lam_abs, min_count, workspace_bytes, system):
+    """The coarse-to-fine Gauss-Newton run that `align` and `tsdf_merge.register_volumes` are, from host poses float64
+    [B,3,4] and checked `levels`.  workspace_bytes(B, min_stride) gives the size of the chunks' workspace at the smallest
+    stride (and raises the caller's ValueError when there is none); system(stride, pose, rows, workspace) enqueues the
+    caller's system for the device poses.  Every level's system / gs_tsdf_align_step pairs and one closing system at the
+    last level's stride are enqueued on the current stream; poses, closing rows and trace are read once.  -> the result
+    both callers document, with the final [B,4,4] matrices as "matrix" and count / considered as "ratio" (a caller gives
+    the two its own names) and rmse_m = trunc * sqrt(sq / count).  ValueError for bad lam_rel, lam_abs or min_count,
+    before the library or the device is reached."""
+    lam_rel, lam_abs = float(lam_rel), float(lam_abs)
+    if not (0 <= lam_rel < math.inf and 0 <= lam_abs < math.inf):
+        raise ValueError(f"{what}: lam_rel and lam_abs must be finite and >= 0 (got {lam_rel}, {lam_abs})")
+    if isinstance(min_count, bool) or int(min_count) != min_count or int(min_count) < 1:
+        raise ValueError(f"{what}: min_count must be an integer >= 1 (got {min_count!r})")
+    min_count = int(min_count)
+    B = int(poses.shape[0])
+    iters = sum(n for _, n in levels)
+    pose, rows, workspace = _buffers(dev, poses, workspace_bytes(B, min(s for s, _ in levels)))
+    trace = torch.zeros(iters, B, 4, dtype=torch.float64, device=dev)
+    it = 0
+    for stride, n in levels:
+        for _ in range(n):
+            system(stride, pose, rows, workspace)
+            with torch.cuda.device(dev):
+                rc = _lib.lib().gs_tsdf_align_step(_lib.ptr(rows), _lib.ptr(pose), B, lam_rel, lam_abs, min_count,
+                                                   _lib.ptr(trace[it]), _lib.stream_ptr(dev))
+            _lib.check(rc, what)
+            it += 1
+    system(levels[-1][0], pose, rows, workspace)
+    host = torch.cat([pose.reshape(-1), rows.reshape(-1), trace.reshape(-1)]).cpu().numpy()                # the one read
+    final = host[:B * 12].reshape(B, 3, 4)
+    closing = host[B * 12:B * 44].reshape(B, 32)
+    tr = host[B * 44:].reshape(iters, B, 4)
+    rmse, share, count = _fit(closing, trunc)
+    T = np.zeros((B, 4, 4), np.float64)
+    T[:, :3, :] = final
+    T[:, 3, 3] = 1.0
+    stepped = tr[-1, :, 3] == 1.0 if iters else np.ones(B, bool)
+    moved = final[:, :, 3] - poses[:, :, 3]
+    constrained_m, n_constrained = constrained_movement(closing, moved)
+    return {"matrix": T, "ok": stepped & (count >= min_count), "rmse_m": rmse, "ratio": share, "count": count, "trace": tr,
+            "moved_m": np.linalg.norm(moved, axis=1), "moved_deg": rotation_angle_deg(final[:, :, :3], poses[:, :, :3]),
+            "moved_constrained_m": constrained_m, "n_constrained": n_constrained}
 
 
 def _fit(rows, trunc):
@@ -170,38 +217,11 @@ def align(vol, depth, c2w_init, intrinsics, frame=None, levels=DEFAULT_LEVELS, h
     depth, poses, fr, intr, huber, max_depth, min_weight = _inputs(vol, what, depth, c2w_init, intrinsics, frame, huber,
                                                                    max_depth, min_weight)
     levels = _levels(levels, what)
-    lam_rel, lam_abs = float(lam_rel), float(lam_abs)
-    if not (0 <= lam_rel < math.inf and 0 <= lam_abs < math.inf):
-        raise ValueError(f"{what}: lam_rel and lam_abs must be finite and >= 0 (got {lam_rel}, {lam_abs})")
-    if isinstance(min_count, bool) or int(min_count) != min_count or int(min_count) < 1:
-        raise ValueError(f"{what}: min_count must be an integer >= 1 (got {min_count!r})")
-    min_count = int(min_count)
-    B = poses.shape[0]
-    iters = sum(n for _, n in levels)
-    sysm = _Systems(vol, depth, poses, fr, intr, huber, max_depth, min_weight, min(s for s, _ in levels), what)
-    trace = torch.zeros(iters, B, 4, dtype=torch.float64, device=vol.device)
-    it = 0
-    for stride, n in levels:
-        for _ in range(n):
-            sysm.system(stride)
-            sysm.step(lam_rel, lam_abs, min_count, trace[it])
-            it += 1
-    sysm.system(levels[-1][0])
-    host = torch.cat([sysm.pose.reshape(-1), sysm.rows.reshape(-1), trace.reshape(-1)]).cpu().numpy()      # the one read
-    final = host[:B * 12].reshape(B, 3, 4)
-    rows = host[B * 12:B * 44].reshape(B, 32)
-    tr = host[B * 44:].reshape(iters, B, 4)
-    rmse, inlier, count = _fit(rows, vol.trunc)
-    c2w = np.zeros((B, 4, 4), np.float64)
-    c2w[:, :3, :] = final
-    c2w[:, 3, 3] = 1.0
-    stepped = tr[-1, :, 3] == 1.0 if iters else np.ones(B, bool)
-    moved = final[:, :, 3] - poses[:, :, 3]
-    constrained_m, n_constrained = constrained_movement(rows, moved)
-    return {"c2w": c2w, "ok": stepped & (count >= min_count), "rmse_m": rmse, "inlier_fraction": inlier, "count": count,
-            "trace": tr, "moved_m": np.linalg.norm(moved, axis=1),
-            "moved_deg": rotation_angle_deg(final[:, :, :3], poses[:, :, :3]),
-            "moved_constrained_m": constrained_m, "n_constrained": n_constrained}
+    sysm = _Systems(vol, depth, fr, intr, huber, max_depth, min_weight, what)
+    res = gauss_newton(what, vol.device, poses, levels, vol.trunc, lam_rel, lam_abs, min_count, sysm.workspace_bytes,
+                       sysm.system)
+    res["c2w"], res["inlier_fraction"] = res.pop("matrix"), res.pop("ratio")
+    return res
 
 
 CONSTRAINED_SHARE = 0.01         # of the largest eigenvalue of H's translation block
@@ -235,9 +255,10 @@ def pose_scores(vol, depth, c2w, intrinsics, frame=None, stride=4, huber=0.5, ma
     if isinstance(stride, bool) or int(stride) != stride or int(stride) < 1:
         raise ValueError(f"{what}: stride must be an integer >= 1 (got {stride!r})")
     stride = int(stride)
-    sysm = _Systems(vol, depth, poses, fr, intr, huber, max_depth, min_weight, stride, what)
-    sysm.system(stride)
-    rmse, inlier, count = _fit(sysm.rows.cpu().numpy(), vol.trunc)                                         # the one read
+    sysm = _Systems(vol, depth, fr, intr, huber, max_depth, min_weight, what)
+    pose, rows, workspace = _buffers(vol.device, poses, sysm.workspace_bytes(int(poses.shape[0]), stride))
+    sysm.system(stride, pose, rows, workspace)
+    rmse, inlier, count = _fit(rows.cpu().numpy(), vol.trunc)                                              # the one read
     return {"rmse_m": rmse, "inlier_fraction": inlier, "count": count}
 
 

@@ -80,60 +80,31 @@ def register_volumes(dst, src, T_init, levels=DEFAULT_LEVELS, huber=0.5, min_wei
         raise ValueError(f"{what}: dst is on {dst.device}, src on {src.device}")
     poses = transforms34(T_init, what)
     levels = _localize._levels(levels, what)
-    huber, min_weight, lam_rel, lam_abs = float(huber), float(min_weight), float(lam_rel), float(lam_abs)
+    huber, min_weight = float(huber), float(min_weight)
     if not huber > 0:
         raise ValueError(f"{what}: huber must be positive, in units of the destination's truncation (got {huber})")
     if math.isnan(min_weight):
         raise ValueError(f"{what}: min_weight is NaN")
-    if not (0 <= lam_rel < math.inf and 0 <= lam_abs < math.inf):
-        raise ValueError(f"{what}: lam_rel and lam_abs must be finite and >= 0 (got {lam_rel}, {lam_abs})")
-    if isinstance(min_count, bool) or int(min_count) != min_count or int(min_count) < 1:
-        raise ValueError(f"{what}: min_count must be an integer >= 1 (got {min_count!r})")
-    min_count = int(min_count)
-    B = int(poses.shape[0])
-    iters = sum(n for _, n in levels)
     dev = dst.device
-    L = _lib.lib()
-    nbytes = L.gs_tsdf_register_workspace_bytes(B, *src.dims, min(s for s, _ in levels))
-    if B and nbytes == 0:
-        raise ValueError(f"{what}: {B} transforms of a {src.dims} lattice are too many for one call")
-    pose = torch.from_numpy(poses).to(dev)
-    rows = torch.empty(B, 32, dtype=torch.float64, device=dev)
-    workspace = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=dev)
-    trace = torch.zeros(iters, B, 4, dtype=torch.float64, device=dev)
 
-    def system(stride):
+    def workspace_bytes(B, min_stride):
+        nbytes = _lib.lib().gs_tsdf_register_workspace_bytes(B, *src.dims, min_stride)
+        if B and nbytes == 0:
+            raise ValueError(f"{what}: {B} transforms of a {src.dims} lattice are too many for one call")
+        return nbytes
+
+    def system(stride, pose, rows, workspace):
         with torch.cuda.device(dev):
-            rc = L.gs_tsdf_register_system(_lib.ptr(dst.tsdf), _lib.ptr(dst.weight), *_lattice_args(dst), _lib.ptr(src.tsdf),
-                                           _lib.ptr(src.weight), *_lattice_args(src), _lib.ptr(pose), B, int(stride),
-                                           min_weight, huber, _lib.ptr(workspace), _lib.ptr(rows), _lib.stream_ptr(dev))
+            rc = _lib.lib().gs_tsdf_register_system(
+                _lib.ptr(dst.tsdf), _lib.ptr(dst.weight), *_lattice_args(dst), _lib.ptr(src.tsdf), _lib.ptr(src.weight),
+                *_lattice_args(src), _lib.ptr(pose), int(pose.shape[0]), int(stride), min_weight, huber, _lib.ptr(workspace),
+                _lib.ptr(rows), _lib.stream_ptr(dev))
         _lib.check(rc, what)
 
-    it = 0
-    for stride, n in levels:
-        for _ in range(n):
-            system(stride)
-            with torch.cuda.device(dev):
-                rc = L.gs_tsdf_align_step(_lib.ptr(rows), _lib.ptr(pose), B, lam_rel, lam_abs, min_count, _lib.ptr(trace[it]),
-                                          _lib.stream_ptr(dev))
-            _lib.check(rc, what)
-            it += 1
-    system(levels[-1][0])
-    host = torch.cat([pose.reshape(-1), rows.reshape(-1), trace.reshape(-1)]).cpu().numpy()                # the one read
-    final = host[:B * 12].reshape(B, 3, 4)
-    closing = host[B * 12:B * 44].reshape(B, 32)
-    tr = host[B * 44:].reshape(iters, B, 4)
-    rmse, overlap, count = _localize._fit(closing, dst.trunc)
-    T = np.zeros((B, 4, 4), np.float64)
-    T[:, :3, :] = final
-    T[:, 3, 3] = 1.0
-    stepped = tr[-1, :, 3] == 1.0 if iters else np.ones(B, bool)
-    moved = final[:, :, 3] - poses[:, :, 3]
-    constrained_m, n_constrained = _localize.constrained_movement(closing, moved)
-    return {"T": T, "ok": stepped & (count >= min_count), "rmse_m": rmse, "overlap": overlap, "count": count, "trace": tr,
-            "moved_m": np.linalg.norm(moved, axis=1),
-            "moved_deg": _localize.rotation_angle_deg(final[:, :, :3], poses[:, :, :3]),
-            "moved_constrained_m": constrained_m, "n_constrained": n_constrained}
+    res = _localize.gauss_newton(what, dev, poses, levels, dst.trunc, lam_rel, lam_abs, min_count, workspace_bytes,
+                                 system)
+    res["T"], res["overlap"] = res.pop("matrix"), res.pop("ratio")
+    return res
 
 
 def inverse32(T):

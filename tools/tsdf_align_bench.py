@@ -77,20 +77,20 @@ def system_ms(vol, depth, c2w, B, stride, reps):
     import torch
     from go_slam_amd import _lib, localize
     frame = (np.arange(B) % K).astype(np.int32)
-    s = localize._Systems(vol, depth, np.ascontiguousarray(c2w[frame, :3, :]), frame, list(INTR), 0.5, float("inf"), 1.0,
-                          stride, "tsdf_align_bench")
-    s.system(stride)                                        # warm-up
+    s = localize._Systems(vol, depth, frame, list(INTR), 0.5, float("inf"), 1.0, "tsdf_align_bench")
+    bufs = localize._buffers(vol.device, np.ascontiguousarray(c2w[frame, :3, :]), s.workspace_bytes(B, stride))
+    s.system(stride, *bufs)                                 # warm-up
     torch.cuda.synchronize()
     gather, total = [], []
     for _ in range(reps):
         with _lib.kernel_timer(DEV) as kt:
             for _ in range(LAUNCHES):
-                s.system(stride)
+                s.system(stride, *bufs)
             torch.cuda.synchronize()
         t = kt.read()
         gather.append(t["tsdf_align_system"][0] / LAUNCHES)
         total.append((t["tsdf_align_system"][0] + t["tsdf_align_sum"][0]) / LAUNCHES)
-    rows = s.rows.cpu().numpy()
+    rows = bufs[1].cpu().numpy()
     return statistics.median(gather), statistics.median(total), float(rows[:, 28].mean())
 
 
