@@ -26,8 +26,8 @@ def empty_volume(dims, lo, voxel, trunc, colors=True):
     return volume(np.ones(dims, F), np.zeros(dims, F), lo, voxel, trunc, np.zeros((3,) + tuple(dims), F) if colors else None)
 
 
-def cell(points, vol):
-    """(g, a, inside, at) of float32 world points [three arrays] in `vol`: g = (p - lo) / voxel, a = floorf(g), inside = 0
+def cell(points, vol, F=F):
+    """(g, a, inside, at) of float32 (`F`) world points [three arrays] in `vol`: g = (p - lo) / voxel, a = floorf(g), inside = 0
     <= a < float(n - 1) on every axis (a NaN fails), at = the linear index of the cell's first corner (0 where outside)."""
     dims = vol["tsdf"].shape
     lo, voxel = [F(v) for v in vol["lo"]], F(vol["voxel"])
@@ -122,10 +122,12 @@ def register(D, S, pose, chunk, levels=AR.DEFAULT_LEVELS, huber=0.5, min_weight=
     return pose, closing, np.array(trace, np.float64).reshape(len(trace), pose.shape[0], 4)
 
 
-def merge(D, S, d2s=None, min_weight=1.0, max_weight=64.0):
+def merge(D, S, d2s=None, min_weight=1.0, max_weight=64.0, dtype=F):
     """gs_tsdf_merge: a new volume dict, D with S fused in, and "touched": bool [nx,ny,nz], the points that were not
     skipped.  d2s: D-world to S-world, [3,4] (rounded to float32 here as the host does; None: the identity).  Colours are
-    fused only when both volumes carry them."""
+    fused only when both volumes carry them.  dtype=np.float64 is the same sequence in double on volumes whose arrays are
+    double: the analytic checks use it, nothing else does."""
+    F = dtype
     if not F(S["trunc"]) >= F(D["trunc"]):
         raise ValueError("merge: trunc_S < trunc_D")
     dims = D["tsdf"].shape
@@ -138,7 +140,7 @@ def merge(D, S, d2s=None, min_weight=1.0, max_weight=64.0):
     with np.errstate(all="ignore"):
         p = [F(D["lo"][r]) + idx[:, r].astype(F) * F(D["voxel"]) for r in range(3)]
         ps = [((m[r, 0] * p[0] + m[r, 1] * p[1]) + m[r, 2] * p[2]) + m[r, 3] for r in range(3)]
-        g, a, inside, at = cell(ps, S)
+        g, a, inside, at = cell(ps, S, F)
         offs = corner_offsets(S["tsdf"].shape)
         wc = [S["weight"].reshape(-1)[at + o] for o in offs]
         keep = inside.copy()
