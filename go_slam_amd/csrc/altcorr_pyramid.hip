@@ -32,7 +32,6 @@
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half2v __attribute__((ext_vector_type(2)));
 typedef float float4v __attribute__((ext_vector_type(4)));
 
@@ -47,12 +46,6 @@ struct AltPyrArgs {
   _Float16* out;                   // [E][H][W][196]
   int E, H, W;
 };
-
-__device__ __forceinline__ void wave_sync_lds_() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 __device__ __forceinline__ int grp16_min(int v) {
 #pragma unroll
@@ -181,7 +174,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         }
       }
     }
-    wave_sync_lds_();
+    gs_wave_lds_sync();
     // ---- bilinear blend (altcorr_kernel.cu:95-130: the four taps around an output, in the reference's order);
     // lane (q, m): pixel m, window columns q and q + 4; output channel = 49 l + 7 tx + iy
     {
@@ -207,7 +200,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         }
       }
     }
-    wave_sync_lds_();                                     // S is overwritten by the next level
+    gs_wave_lds_sync();                                     // S is overwritten by the next level
   }
   // ---- the tile's 16 x 196 outputs: 392-byte pixel rows, pixels of a tile row adjacent in memory
   uint32_t* out32 = reinterpret_cast<uint32_t*>(A.out) + (size_t)e * hw * 98;

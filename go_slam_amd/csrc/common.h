@@ -194,7 +194,32 @@ __device__ __forceinline__ void gs_retr_se3(const float* xi, const float* t, con
   t1[2] = r[2] + dt[2];
 }
 
+// ---------------------------------------------------------------- MFMA operand vectors -
+typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+typedef _Float16 half4 __attribute__((ext_vector_type(4)));
+typedef float float16v __attribute__((ext_vector_type(16)));
+
+__device__ __forceinline__ half8 ld8(const _Float16* p) { return *reinterpret_cast<const half8*>(p); }
+
+// The lanes of ONE wave hand data to each other through a wave-private LDS tile: release, wave barrier, acquire.
+__device__ __forceinline__ void gs_wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // ---------------------------------------------------------------- wave64 reductions ----
+// inclusive prefix product over lanes (lane k gets prod_{j<=k} v_j)
+__device__ __forceinline__ float wave_incl_prod(float v, int lane) {
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const float u = __shfl_up(v, off, 64);
+    if (lane >= off) v = v * u;
+  }
+  return v;
+}
+
+
 // Sum across the 64 lanes of a wave: 4 DPP steps inside each 16-lane row (quad_perm xor 1,
 // xor 2, row_half_mirror, row_mirror) then the four row totals are combined through scalar
 // registers.  Every lane returns the full sum; the order is fixed => deterministic.

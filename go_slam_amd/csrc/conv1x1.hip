@@ -19,9 +19,6 @@
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float float16v __attribute__((ext_vector_type(16)));
 struct __attribute__((packed, aligned(8))) half8_a8 { half8 v; };   // pixel rows of 196 halves are 8-B aligned
 
 // 16-byte piece `c` of a dense chunk of `avail` halves; the last piece of a chunk whose length is 4 mod 8 is 8 bytes

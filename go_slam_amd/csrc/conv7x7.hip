@@ -24,9 +24,6 @@
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float float16v __attribute__((ext_vector_type(16)));
 
 constexpr int kKSteps = 14;                 // 7 kernel rows x 2 (taps 0-3, taps 4-7)
 constexpr int kScratchRow = 72;             // halves per pixel row of the transpose scratch: 64 + 8 (144 B, 16 B-aligned)

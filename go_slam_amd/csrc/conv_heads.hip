@@ -14,8 +14,6 @@
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float float16v __attribute__((ext_vector_type(16)));
 
 constexpr int HEAD_ROWS = 6;      // output rows per workgroup
 

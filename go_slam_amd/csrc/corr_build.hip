@@ -18,9 +18,6 @@
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float float16v __attribute__((ext_vector_type(16)));
 
 constexpr int KDIM = 128;
 constexpr int BM = 64;          // source pixels per workgroup: every target-row fragment read from L2 feeds two MFMAs
@@ -90,7 +87,6 @@ __global__ __launch_bounds__(256) void corr_prep_kernel(const _Float16* __restri
   }
 }
 
-__device__ __forceinline__ half8 ld8(const _Float16* p) { return *reinterpret_cast<const half8*>(p); }
 
 __global__ __launch_bounds__(256, 3) void corr_volume_kernel(
     const _Float16* __restrict__ f1t, const _Float16* __restrict__ f2t, _Float16* __restrict__ v0,

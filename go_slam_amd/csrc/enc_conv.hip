@@ -26,9 +26,6 @@
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float float16v __attribute__((ext_vector_type(16)));
 
 struct EncArgs {
   float* stats;                       // [n][workgroups per image][cout] (count, mean, M2) of v, or nullptr

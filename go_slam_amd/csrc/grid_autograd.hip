@@ -47,17 +47,9 @@ __global__ __launch_bounds__(256) void grid_backward_kernel(GridBwdArgs A, gs_gr
   float dxa[3] = {0.f, 0.f, 0.f};
 #pragma unroll 1
   for (int l = 0; l < GS_GRID_LEVELS; ++l) {
-    const float scale = m.scale[l];
+    uint32_t g[3], cidx[8];
     float f[3];
-    uint32_t g[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      const float pos = fmaf(scale, xi[d], 0.5f);
-      const float fl = floorf(pos);
-      g[d] = (uint32_t)(int)fl;
-      f[d] = pos - fl;
-    }
-    uint32_t cidx[8];
+    const float scale = grid_cell(m, l, xi, g, f);
     grid_corners(m, l, g, cidx);
     float dyl[2];
     if (A.dy16) {
@@ -68,59 +60,35 @@ __global__ __launch_bounds__(256) void grid_backward_kernel(GridBwdArgs A, gs_gr
       dyl[0] = p[0] * A.dy_scale; dyl[1] = p[1] * A.dy_scale;
     }
     if (!on) { dyl[0] = 0.f; dyl[1] = 0.f; }
-    // per-dimension interpolation factors of the 8 corners: wd[d][bit]
-    float wd[3][2];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) { wd[d][0] = 1.0f - f[d]; wd[d][1] = f[d]; }
-
     if (want_gg) {
-      float gacc[8][2];
+      float gacc[8][2], wc[8];
+      if (!SECOND) {
+        grid_weights(f, wc);
+      } else {          // directional derivative of the corner weight along v; wd[d][bit] = the factor of axis d
+        float wd[3][2];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) { wd[d][0] = 1.0f - f[d]; wd[d][1] = f[d]; }
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+          const int b0 = c & 1, b1 = (c >> 1) & 1, b2 = (c >> 2) & 1;
+          const float s0 = b0 ? scale : -scale, s1 = b1 ? scale : -scale, s2 = b2 ? scale : -scale;
+          wc[c] = vv[0] * s0 * (wd[1][b1] * wd[2][b2]) + vv[1] * s1 * (wd[0][b0] * wd[2][b2]) +
+                  vv[2] * s2 * (wd[0][b0] * wd[1][b1]);
+        }
+      }
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
-        const int b0 = c & 1, b1 = (c >> 1) & 1, b2 = (c >> 2) & 1;
-        float w;
-        if (!SECOND) {
-          w = wd[0][b0] * wd[1][b1] * wd[2][b2];
-        } else {        // directional derivative of the corner weight along v
-          const float s0 = b0 ? scale : -scale, s1 = b1 ? scale : -scale, s2 = b2 ? scale : -scale;
-          w = vv[0] * s0 * (wd[1][b1] * wd[2][b2]) + vv[1] * s1 * (wd[0][b0] * wd[2][b2]) +
-              vv[2] * s2 * (wd[0][b0] * wd[1][b1]);
-        }
-        gacc[c][0] = w * dyl[0] * s32;
-        gacc[c][1] = w * dyl[1] * s32;
+        gacc[c][0] = wc[c] * dyl[0] * s32;
+        gacc[c][1] = wc[c] * dyl[1] * s32;
       }
       float* tab = A.gg32 ? A.gg32 + (size_t)m.offset[l] * 2 : nullptr;
       _Float16* tab16 = A.gg16 ? A.gg16 + (size_t)m.offset[l] * 2 : nullptr;
       lvl_scatter(tab, tab16, A.gg_scale, cidx, gacc, g, on, lane);
     }
     if (want_vals) {
-      const _Float16* tabv = A.grid + (size_t)m.offset[l] * 2;
-      float val[8][2];
-#pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        const uint32_t raw = *reinterpret_cast<const uint32_t*>(tabv + (size_t)cidx[c] * 2);
-        val[c][0] = (float)__builtin_bit_cast(_Float16, (uint16_t)(raw & 0xffffu));
-        val[c][1] = (float)__builtin_bit_cast(_Float16, (uint16_t)(raw >> 16));
-      }
-      // first derivatives d y_f / d x_gd (same accumulation order as the forward kernel's dy_dx)
-      float dv[3][2];
-#pragma unroll
-      for (int gd = 0; gd < 3; ++gd) {
-        const int o0 = (gd == 0) ? 1 : 0, o1 = (gd == 2) ? 1 : 2;
-        float a0 = 0.f, a1 = 0.f;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          float w = scale;
-          w = w * wd[o0][k & 1];
-          w = w * wd[o1][(k >> 1) & 1];
-          const int cl = ((k & 1) << o0) | (((k >> 1) & 1) << o1);
-          const int cr = cl | (1 << gd);
-          a0 = fmaf(w, val[cr][0] - val[cl][0], a0);
-          a1 = fmaf(w, val[cr][1] - val[cl][1], a1);
-        }
-        dv[gd][0] = a0;
-        dv[gd][1] = a1;
-      }
+      float val[8][2], dv[3][2];
+      grid_gather(A.grid + (size_t)m.offset[l] * 2, cidx, val);
+      grid_dvalue(scale, f, val, dv);     // (the forward kernel's dy_dx)
       if (!SECOND) {
 #pragma unroll
         for (int d = 0; d < 3; ++d) dxa[d] += dyl[0] * dv[d][0] + dyl[1] * dv[d][1];
@@ -136,15 +104,13 @@ __global__ __launch_bounds__(256) void grid_backward_kernel(GridBwdArgs A, gs_gr
           for (int a = 0; a < 3; ++a)
 #pragma unroll
             for (int b = a + 1; b < 3; ++b) {
-              const int t = 3 - a - b;
               float h0 = 0.f, h1 = 0.f;
 #pragma unroll
               for (int k = 0; k < 2; ++k) {
-                const int base = k << t;
-                const int c11 = base | (1 << a) | (1 << b), c10 = base | (1 << a), c01 = base | (1 << b), c00 = base;
-                const float w = scale * scale * wd[t][k];
-                h0 = fmaf(w, (val[c11][0] - val[c10][0]) - (val[c01][0] - val[c00][0]), h0);
-                h1 = fmaf(w, (val[c11][1] - val[c10][1]) - (val[c01][1] - val[c00][1]), h1);
+                const GridD2 q = grid_d2(a, b, k);
+                const float w = scale * scale * (k ? f[q.t] : 1.0f - f[q.t]);
+                h0 = fmaf(w, (val[q.c11][0] - val[q.c10][0]) - (val[q.c01][0] - val[q.c00][0]), h0);
+                h1 = fmaf(w, (val[q.c11][1] - val[q.c10][1]) - (val[q.c01][1] - val[q.c00][1]), h1);
               }
               const float hab = dyl[0] * h0 + dyl[1] * h1;
               dxa[a] += hab * vv[b];

@@ -12,7 +12,6 @@
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ float sigm(float x) { return gs_sigmoid(x); }
 

@@ -21,7 +21,6 @@
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
 constexpr int IN_CHUNK = 256;      // pixels per statistics workgroup
 

@@ -16,7 +16,6 @@
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
 // grads: element i < n16 comes from g16 (fp16, value * inv_scale16), element i >= n16 from g32[i - n16]
 __global__ __launch_bounds__(256) void map_grad_sqnorm_kernel(const _Float16* __restrict__ g16, size_t n16,

@@ -24,9 +24,6 @@
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float float16v __attribute__((ext_vector_type(16)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));   // (a native vector: what the non-temporal builtins take)
 
 // ---------------------------------------------------------------------------------------
@@ -165,59 +162,6 @@ __global__ __launch_bounds__(256) void render_sample_wave_kernel(
 // ---------------------------------------------------------------------------------------
 // hash grid
 // ---------------------------------------------------------------------------------------
-// One level: value (2 features) and d value / d x (3 x 2), tcnn accumulation order.
-__device__ __forceinline__ void grid_level(const gs_grid_meta& m, int l, const _Float16* __restrict__ grid,
-                                           const float x[3], float val[2], float dv[3][2], bool want_grad) {
-  const float scale = m.scale[l];
-  float f[3];
-  uint32_t g[3];
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    const float pos = fmaf(scale, x[d], 0.5f);
-    const float fl = floorf(pos);
-    g[d] = (uint32_t)(int)fl;
-    f[d] = pos - fl;
-  }
-  const _Float16* tab = grid + (size_t)m.offset[l] * 2;
-  float v[8][2];
-  uint32_t cidx[8];
-  grid_corners(m, l, g, cidx);
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    const uint32_t raw = *reinterpret_cast<const uint32_t*>(tab + (size_t)cidx[c] * 2);
-    v[c][0] = (float)__builtin_bit_cast(_Float16, (uint16_t)(raw & 0xffffu));
-    v[c][1] = (float)__builtin_bit_cast(_Float16, (uint16_t)(raw >> 16));
-  }
-  val[0] = 0.f; val[1] = 0.f;
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    float w = 1.0f;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) w = w * (((c >> d) & 1) ? f[d] : (1.0f - f[d]));
-    val[0] = fmaf(w, v[c][0], val[0]);
-    val[1] = fmaf(w, v[c][1], val[1]);
-  }
-  if (want_grad) {
-#pragma unroll
-    for (int gd = 0; gd < 3; ++gd) {
-      const int o0 = (gd == 0) ? 1 : 0, o1 = (gd == 2) ? 1 : 2;   // the two other dims, ascending
-      float a0 = 0.f, a1 = 0.f;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        float w = scale;
-        w = w * ((k & 1) ? f[o0] : (1.0f - f[o0]));
-        w = w * ((k & 2) ? f[o1] : (1.0f - f[o1]));
-        const int cl = ((k & 1) << o0) | (((k >> 1) & 1) << o1);
-        const int cr = cl | (1 << gd);
-        a0 = fmaf(w, v[cr][0] - v[cl][0], a0);
-        a1 = fmaf(w, v[cr][1] - v[cl][1], a1);
-      }
-      dv[gd][0] = a0;
-      dv[gd][1] = a1;
-    }
-  }
-}
-
 __global__ __launch_bounds__(256) void grid_encode_kernel(const float* __restrict__ x,
                                                           const _Float16* __restrict__ grid,
                                                           _Float16* __restrict__ out, float* __restrict__ dy_dx,
@@ -228,7 +172,7 @@ __global__ __launch_bounds__(256) void grid_encode_kernel(const float* __restric
 #pragma unroll 1
   for (int l = 0; l < GS_GRID_LEVELS; ++l) {
     float val[2], dv[3][2];
-    grid_level(m, l, grid, xi, val, dv, dy_dx != nullptr);
+    grid_encode_level(m, l, grid, xi, val, dv, dy_dx != nullptr);
     out[(size_t)i * 32 + 2 * l + 0] = (_Float16)val[0];
     out[(size_t)i * 32 + 2 * l + 1] = (_Float16)val[1];
     if (dy_dx) {
@@ -248,8 +192,6 @@ __global__ __launch_bounds__(256) void grid_encode_kernel(const float* __restric
 //                                  point 32*nt + (l&31)
 // ---------------------------------------------------------------------------------------
 constexpr int HS = 72;   // LDS row stride (halfs) of the wave-private activation tile [64][64]
-
-__device__ __forceinline__ half8 ld8(const _Float16* p) { return *reinterpret_cast<const half8*>(p); }
 
 template <bool RELU>
 __device__ __forceinline__ void store_act(_Float16* hs, const float16v& c, int mt, int nt, int lane) {
@@ -289,12 +231,6 @@ __device__ __forceinline__ void store_act_xs(_Float16* xs, const float16v& c, in
   }
 }
 
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __device__ __forceinline__ void wave_mlp64(_Float16* xs, const _Float16* __restrict__ w, int lane, float16v (&co)[2]) {
   const _Float16* W1 = w;                 // [64][80]
   const _Float16* W2 = w + 64 * 80;       // [64][64]
@@ -323,12 +259,12 @@ __device__ __forceinline__ void wave_mlp64(_Float16* xs, const _Float16* __restr
         for (int mt = 0; mt < 2; ++mt) c[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[mt][ks], b, c[mt][nt], 0, 0, 0);
       }
   }
-  wave_lds_sync();                        // every lane has read its input rows: the tile now takes the activations
+  gs_wave_lds_sync();                        // every lane has read its input rows: the tile now takes the activations
 #pragma unroll
   for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) store_act_xs<true>(xs, c[mt][nt], mt, nt, lane);
-  wave_lds_sync();
+  gs_wave_lds_sync();
   // ---- layer 2
   {
     half8 a[2][4], bfr[2][4];
@@ -354,12 +290,12 @@ __device__ __forceinline__ void wave_mlp64(_Float16* xs, const _Float16* __restr
         for (int mt = 0; mt < 2; ++mt)
           c[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[mt][ks], bfr[nt][ks], c[mt][nt], 0, 0, 0);
   }
-  wave_lds_sync();
+  gs_wave_lds_sync();
 #pragma unroll
   for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) store_act_xs<true>(xs, c[mt][nt], mt, nt, lane);
-  wave_lds_sync();
+  gs_wave_lds_sync();
   // ---- output layer (16 rows, padded to the 32-row tile with zero weights)
   {
     half8 a3[4];
@@ -418,20 +354,6 @@ __device__ __forceinline__ bool point_of(const NeusArgs& A, int idx, float pt[3]
   return (pt[0] < rb[1]) && (pt[0] > rb[0]) && (pt[1] < rb[3]) && (pt[1] > rb[2]) && (pt[2] < rb[5]) && (pt[2] > rb[4]);
 }
 
-// normalized_3d_coordinate (InstantNeuS.py:12-32) with the STATIC bound, clamped to [-1,1]; `view` = the grid's [0,1] input
-__device__ __forceinline__ void normalise_point(const NeusArgs& A, const float pt[3], float p[3], float view[3],
-                                                float inside[3], float span[3]) {
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    span[d] = A.bound[2 * d + 1] - A.bound[2 * d];
-    float q = (pt[d] - A.bound[2 * d]) / span[d] * 2.0f - 1.0f;
-    inside[d] = (q >= -1.0f && q <= 1.0f) ? 1.0f : 0.0f;
-    q = fminf(fmaxf(q, -1.0f), 1.0f);
-    p[d] = q;
-    view[d] = (q + 1.0f) / 2.0f;
-  }
-}
-
 // ---------------------------------------------------------------------------------------
 // LEVEL-MAJOR encode of the hashed levels (round 5).  The 11 hashed levels are 2 MB tables each (2^19 entries x 4 B);
 // a point-major kernel walks all 16 levels per point, so every XCD streams the whole 25 MB table through its 4 MB L2
@@ -459,9 +381,9 @@ __global__ __launch_bounds__(256) void neus_encode_levels_kernel(NeusArgs A, gs_
   float pt[3], dir[3], zm, dist;
   if (!point_of(A, idx, pt, dir, zm, dist)) return;      // (out-of-bound points have no record: nobody reads one)
   float p[3], view[3], inside[3], span[3];
-  normalise_point(A, pt, p, view, inside, span);
+  normalise_point(A.bound, pt, p, view, inside, span);
   float val[2], dv[3][2];
-  grid_level(m, l, A.grid, view, val, dv, true);
+  grid_encode_level(m, l, A.grid, view, val, dv, true);
   typedef const __attribute__((address_space(4))) float* cfp;    // uniform, unchanged during the launch -> s_load
   cfp wl = (cfp)(uintptr_t)(A.sdf_w + 3 + 2 * l);
   const float g0 = (float)(_Float16)wl[0], g1 = (float)(_Float16)wl[1];     // dL/d enc arrives as fp16
@@ -576,7 +498,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     for (int q = 0; q < 10; ++q) xrow[q] = zero;
   } else {
     float p[3], view[3], inside[3], span[3];
-    normalise_point(A, pt, p, view, inside, span);
+    normalise_point(A.bound, pt, p, view, inside, span);
     // Linear(35 -> 32): xyz part first, then one level (2 inputs) at a time
     float out[32];
   #pragma unroll
@@ -593,7 +515,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     for (int l = 0; l < l_rec; ++l) {
       const float* wl = A.sdf_w + 3 + 2 * l;
       float val[2], dv[3][2];
-      grid_level(m, l, A.grid, view, val, dv, true);
+      grid_encode_level(m, l, A.grid, view, val, dv, true);
       const float e0 = (float)(_Float16)val[0], e1 = (float)(_Float16)val[1];   // encoding output is fp16
       if (enc_aux) {  // training: what the backward needs of this level's 8 corner values -- the encoding and d enc / d x --
                       // as one 16-byte record [level][point][8], so that it streams them instead of gathering again
@@ -651,11 +573,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     // NeuS alpha (InstantNeuS.py:276-293), cos_anneal_ratio = 1
     const float true_cos = (dir[0] * grad[0] + dir[1] * grad[1]) + dir[2] * grad[2];
     const float iter_cos = -(fmaxf(-true_cos * 0.5f + 0.5f, 0.0f) * 0.0f + fmaxf(-true_cos, 0.0f) * 1.0f);
-    const float est_next = sdf + iter_cos * dist / 2.0f;
-    const float est_prev = sdf - iter_cos * dist / 2.0f;
-    const float inv_s_ = A.inv_s_dev ? *A.inv_s_dev : A.inv_s;
-    const float prev_cdf = 1.0f / (1.0f + expf(-(est_prev * inv_s_)));
-    const float next_cdf = 1.0f / (1.0f + expf(-(est_next * inv_s_)));
+    float est_prev, est_next, prev_cdf, next_cdf;
+    neus_cdf_pair(sdf, iter_cos, dist, A.inv_s_dev ? *A.inv_s_dev : A.inv_s, est_prev, est_next, prev_cdf, next_cdf);
     float alpha = (prev_cdf - next_cdf + 1e-5f) / (prev_cdf + 1e-5f);
     alpha = fminf(fmaxf(alpha, 0.0f), 1.0f);
     sdf_out[idx] = sdf;
@@ -682,7 +601,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     }
   }
   // ---- the colour MLP of this wave's 64 points (tcnn FullyFusedMLP 67(->80)->64->64->3, ReLU, then sigmoid)
-  wave_lds_sync();
+  gs_wave_lds_sync();
   float16v co[2];
   wave_mlp64(xs, mlp_w, lane, co);
   const int wave_p0 = (force_pass ? p0 : blockIdx.x * 256) + (threadIdx.x >> 6) * 64;
@@ -827,15 +746,6 @@ __global__ __launch_bounds__(256) void mlp_pad_kernel(const _Float16* __restrict
 // ---------------------------------------------------------------------------------------
 // One wave per ray: lanes own samples (64 per pass), the exclusive transmittance product is a
 // wave prefix scan, the per-ray sums are wave reductions; every load is coalesced.
-__device__ __forceinline__ float wave_incl_prod(float v, int lane) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const float u = __shfl_up(v, off, 64);
-    if (lane >= off) v = v * u;
-  }
-  return v;
-}
-
 __global__ __launch_bounds__(256) void neus_ray_kernel(const float* __restrict__ alpha, const _Float16* __restrict__ rgb,
                                                        const float* __restrict__ zmid, const float* __restrict__ grad,
                                                        const uint8_t* __restrict__ mask, float* __restrict__ color,

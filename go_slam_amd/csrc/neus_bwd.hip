@@ -41,15 +41,6 @@
 
 namespace {
 
-__device__ __forceinline__ float wave_incl_prod(float v, int lane) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const float u = __shfl_up(v, off, 64);
-    if (lane >= off) v = v * u;
-  }
-  return v;
-}
-
 // inclusive suffix sum over lanes (lane k gets sum_{j>=k} v_j)
 __device__ __forceinline__ float wave_incl_suffix_sum(float v, int lane) {
 #pragma unroll
@@ -199,11 +190,6 @@ __device__ __forceinline__ void load_dx40(const BwdArgs& A, int i, int c, float*
 // unrelated addresses into every store instruction (138 of them per point), which the write path handles
 // at a fraction of HBM speed; the tile turns them into contiguous 16-byte pieces of the wave's 64 rows.
 constexpr int ROW_TS = 41;                       // tile row stride in dwords (lin 20 | w0 20 | pad)
-__device__ __forceinline__ void wave_sync_lds() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 // store `ndw` dwords per point (a multiple of 4) from tile[point][off .. off+ndw) to rows of `ndw` dwords
 // `stride16` = distance between consecutive points' rows in 16-byte units (0: rows are contiguous)
 __device__ __forceinline__ void tile_flush(const uint32_t* __restrict__ tile, int off, int ndw, void* __restrict__ base,
@@ -230,7 +216,73 @@ __device__ __forceinline__ void st_row(void* base, bool h16, size_t idx, float v
   else reinterpret_cast<float*>(base)[idx] = v;
 }
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+// The opening both per-point backward kernels share: the point's loads, its position, the total dL/dsdf and dL/dgrad
+// (eikonal term and the NeuS-alpha chain included) and the static-bound normalisation.  `d_inv_s` is what
+// neus_point_bwd_kernel reduces, `ddir` (dL / d dir of the cos term) what neus_point_raygrad_kernel adds; a caller that
+// ignores one does not pay for it.
+struct PointHead {
+  float pt[3], zm, live;
+  float dov[32];                       // dL / d (SDF network output): [total d sdf | d feat (31)]
+  float dg[3], d_inv_s, ddir[3];       // total dL / d grad
+  float p[3], view[3], inside[3], span[3];
+};
+__device__ __forceinline__ void point_head(const BwdArgs& A, int i, bool on, PointHead& h) {
+  const int ray = i / A.s;
+  // ---- every input of the point is REQUESTED here, before anything is computed from it (see load_dx40: the round-5 form
+  // interleaved loads, branches and first uses, and its head was a chain of ~10 dependent memory round trips)
+  const uint8_t mk = A.mask[i];
+  const float dist = A.dists[i], zv = A.z_vals[i], sdf = A.sdf[i];
+  const float d_sdf_in = A.d_sdf[i], da_in = A.d_alpha[i], gerr_ray = A.d_gerr_ray[ray];
+  float g[3], dg_in[3], dir[3], org[3];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    g[d] = A.grad[i * 3 + d];
+    dg_in[d] = A.d_grad[i * 3 + d];
+    dir[d] = A.rays_d[ray * 3 + d];
+    org[d] = A.rays_o[ray * 3 + d];
+  }
+  const float inv_s_ = A.inv_s_dev ? *A.inv_s_dev : A.inv_s;
+  // colour-MLP input gradient row dX[i, 32:72] (normal / feature part; the embedding part is re-read at the
+  // end so that it does not occupy registers across the level loop)
+  float dxh[40];
+  load_dx40(A, i, 32, dxh);
+  // lanes that are out of bound / past the end carry zero upstream gradients
+  h.live = (on && mk != 0) ? 1.0f : 0.0f;
+  h.zm = zv + dist / 2.0f;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) h.pt[d] = org[d] + dir[d] * h.zm;
+  // ---- total gradient w.r.t. sdf and grad ----------------------------------------------------
+  float d_sdf = d_sdf_in * h.live;
+  const float gn = sqrtf((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]);
+  const float eik = (gn > 0.f) ? gerr_ray * 2.0f * (gn - 1.0f) / gn : 0.0f;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) { h.dg[d] = (dg_in[d] + eik * g[d] + dxh[1 + d]) * h.live; h.ddir[d] = 0.f; }
+  h.d_inv_s = 0.f;
+  {   // NeuS alpha (InstantNeuS.py:276-293)
+    const float da = da_in * h.live;
+    const float cosv = (dir[0] * g[0] + dir[1] * g[1]) + dir[2] * g[2];
+    float est_prev, est_next, p, q;
+    neus_cdf_pair(sdf, -fmaxf(-cosv, 0.0f), dist, inv_s_, est_prev, est_next, p, q);
+    const float raw = (p - q + 1e-5f) / (p + 1e-5f);
+    if (da != 0.0f && raw >= 0.0f && raw <= 1.0f) {    // torch.clip passes the gradient on [min, max]
+      const float dp = da * q / ((p + 1e-5f) * (p + 1e-5f));
+      const float dq = -da / (p + 1e-5f);
+      const float dprev = dp * p * (1.0f - p), dnext = dq * q * (1.0f - q);
+      h.d_inv_s = dprev * est_prev + dnext * est_next;
+      d_sdf += (dprev + dnext) * inv_s_;
+      const float dc = (dnext - dprev) * inv_s_ * dist / 2.0f;
+      if (cosv < 0.0f) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) { h.dg[d] += dc * dir[d]; h.ddir[d] = dc * g[d]; }
+      }
+    }
+  }
+  normalise_point(A.bound, h.pt, h.p, h.view, h.inside, h.span);
+  h.dov[0] = d_sdf;
+#pragma unroll
+  for (int o = 1; o < 32; ++o) h.dov[o] = dxh[4 + (o - 1)] * h.live;
+}
+
 template <bool BINNED, bool AUX>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void neus_point_bwd_kernel(BwdArgs A, gs_grid_meta m) {
   __shared__ float red[4];
@@ -257,85 +309,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void n
   const int np = A.n * A.s;
   const bool valid = idx < np;
   const int i = valid ? idx : np - 1;
-  const int ray = i / A.s;
-  // ---- every input of the point is REQUESTED here, before anything is computed from it (see load_dx40: the round-5 form
-  // interleaved loads, branches and first uses, and its head was a chain of ~10 dependent memory round trips)
-  const uint8_t mk = A.mask[i];
-  const float dist = A.dists[i], zv = A.z_vals[i], sdf = A.sdf[i];
-  const float d_sdf_in = A.d_sdf[i], da_in = A.d_alpha[i], gerr_ray = A.d_gerr_ray[ray];
-  float g[3], dg_in[3], dir[3], org[3];
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    g[d] = A.grad[i * 3 + d];
-    dg_in[d] = A.d_grad[i * 3 + d];
-    dir[d] = A.rays_d[ray * 3 + d];
-    org[d] = A.rays_o[ray * 3 + d];
-  }
-  const float inv_s_ = A.inv_s_dev ? *A.inv_s_dev : A.inv_s;
-  // colour-MLP input gradient row dX[i, 32:72] (normal / feature part; the embedding part is re-read at the
-  // end so that it does not occupy registers across the level loop)
-  float dxh[40];
-  load_dx40(A, i, 32, dxh);
-  const bool on = valid && mk != 0;
-  const float zm = zv + dist / 2.0f;
-  float pt[3];
-#pragma unroll
-  for (int d = 0; d < 3; ++d) pt[d] = org[d] + dir[d] * zm;
+  PointHead h;
+  point_head(A, i, valid, h);
+  const float live = h.live;
+  const bool on = live != 0.0f;
+  const float (&pt)[3] = h.pt, (&p_)[3] = h.p, (&view)[3] = h.view, (&dov)[32] = h.dov;
   if (valid && !A.rows16) {
     const size_t o3 = (size_t)i * 3;
     st_row(A.pts, false, o3 + 0, pt[0]); st_row(A.pts, false, o3 + 1, pt[1]); st_row(A.pts, false, o3 + 2, pt[2]);
   }
-  // Every lane runs the whole body (wave-level run reduction below needs uniform control flow);
-  // lanes that are out of bound / past the end carry zero upstream gradients and store nothing.
-  const float live = on ? 1.0f : 0.0f;
-  // ---- total gradient w.r.t. sdf and grad ----------------------------------------------------
-  float d_sdf = d_sdf_in * live;
-  float dg[3];
-  const float gn = sqrtf((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]);
-  const float eik = (gn > 0.f) ? gerr_ray * 2.0f * (gn - 1.0f) / gn : 0.0f;
+  // Every lane runs the whole body (wave-level run reduction below needs uniform control flow); dead lanes store nothing.
+  float dG[3];
 #pragma unroll
-  for (int d = 0; d < 3; ++d) dg[d] = (dg_in[d] + eik * g[d] + dxh[1 + d]) * live;
-  float d_invs_local = 0.f;
-  {   // NeuS alpha (InstantNeuS.py:276-293)
-    const float da = da_in * live;
-    const float cosv = (dir[0] * g[0] + dir[1] * g[1]) + dir[2] * g[2];
-    const float c = -fmaxf(-cosv, 0.0f);
-    const float est_next = sdf + c * dist / 2.0f, est_prev = sdf - c * dist / 2.0f;
-    const float p = 1.0f / (1.0f + expf(-(est_prev * inv_s_)));
-    const float q = 1.0f / (1.0f + expf(-(est_next * inv_s_)));
-    const float raw = (p - q + 1e-5f) / (p + 1e-5f);
-    if (da != 0.0f && raw >= 0.0f && raw <= 1.0f) {    // torch.clip passes the gradient on [min, max]
-      const float dp = da * q / ((p + 1e-5f) * (p + 1e-5f));
-      const float dq = -da / (p + 1e-5f);
-      const float dprev = dp * p * (1.0f - p), dnext = dq * q * (1.0f - q);
-      d_invs_local = dprev * est_prev + dnext * est_next;
-      d_sdf += (dprev + dnext) * inv_s_;
-      const float dc = (dnext - dprev) * inv_s_ * dist / 2.0f;
-      if (cosv < 0.0f) {
-#pragma unroll
-        for (int d = 0; d < 3; ++d) dg[d] += dc * dir[d];
-      }
-    }
-  }
-  // ---- SDF network -------------------------------------------------------------------------------
-  float p_[3], view[3], dG[3];
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    const float span = A.bound[2 * d + 1] - A.bound[2 * d];
-    float qn = (pt[d] - A.bound[2 * d]) / span * 2.0f - 1.0f;
-    const float inside = (qn >= -1.0f && qn <= 1.0f) ? 1.0f : 0.0f;
-    qn = fminf(fmaxf(qn, -1.0f), 1.0f);
-    p_[d] = qn;
-    view[d] = (qn + 1.0f) / 2.0f;
-    dG[d] = dg[d] * inside * 2.0f / span;
-  }
+  for (int d = 0; d < 3; ++d) dG[d] = h.dg[d] * h.inside[d] * 2.0f / h.span[d];
   const bool r16 = A.rows16 != 0;
   const float rs = A.row_scale;
   const size_t o32 = (size_t)i * 32, o35 = (size_t)i * 35;
-  float dov[32];
-  dov[0] = d_sdf;
-#pragma unroll
-  for (int o = 1; o < 32; ++o) dov[o] = dxh[4 + (o - 1)] * live;
   if (r16) {                                     // lin | w0 rows are built in this lane's tile row
 #pragma unroll
     for (int d = 0; d < 3; ++d) { tile_h[d] = (_Float16)(p_[d] * live); tile_h[40 + d] = (_Float16)(dG[d] * rs); }
@@ -350,35 +339,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void n
   BSTAMP(0);
 #pragma unroll 1
   for (int l = 0; l < GS_GRID_LEVELS; ++l) {
-    const float scale = m.scale[l];
-    float f[3];
-    uint32_t gi[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      const float pos = fmaf(scale, view[d], 0.5f);
-      const float fl = floorf(pos);
-      gi[d] = (uint32_t)(int)fl;
-      f[d] = pos - fl;
-    }
+    uint32_t gi[3], cidx[8];
+    float f[3], v[8][2], wc[8], e[2];
+    float scale;
     const size_t off = (size_t)m.offset[l];
-    uint32_t cidx[8];
-    float v[8][2];
-    float wc[8], e0 = 0.f, e1 = 0.f;
     half8 rec;
     if constexpr (AUX) {   // the forward kept this level's encoding and d enc / d x: one coalesced 16-byte load, no gathers
       // (requesting the next level's record here, one level ahead, was measured: 5 % slower at both batch sizes)
+      scale = grid_cell(m, l, view, gi, f);
       rec = *reinterpret_cast<const half8*>(A.enc_aux + ((size_t)l * (size_t)np + i) * 8);
       grid_corners(m, l, gi, cidx);
-#pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        float w = 1.0f;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) w = w * (((c >> d) & 1) ? f[d] : (1.0f - f[d]));
-        wc[c] = w;
-      }
-      e0 = on ? (float)rec[0] : 0.0f;          // (out-of-bound points have no record: select, never multiply)
-      e1 = on ? (float)rec[1] : 0.0f;
+      grid_weights(f, wc);
+      e[0] = on ? (float)rec[0] : 0.0f;        // (out-of-bound points have no record: select, never multiply)
+      e[1] = on ? (float)rec[1] : 0.0f;
     } else {
+      // (gather, weights and value stay written out here: composed from grid_gather / grid_weights / grid_value the binned
+      // instantiation took 215 instead of 199 VGPRs and ran 1 % slower; DESIGN section 4.  Same operations, same order.)
+      scale = grid_cell(m, l, view, gi, f);
       grid_corners(m, l, gi, cidx);
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
@@ -386,14 +363,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void n
         v[c][0] = (float)__builtin_bit_cast(_Float16, (uint16_t)(raw & 0xffffu));
         v[c][1] = (float)__builtin_bit_cast(_Float16, (uint16_t)(raw >> 16));
       }
+      e[0] = 0.f; e[1] = 0.f;
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
         float w = 1.0f;
 #pragma unroll
         for (int d = 0; d < 3; ++d) w = w * (((c >> d) & 1) ? f[d] : (1.0f - f[d]));
         wc[c] = w;
-        e0 = fmaf(w, v[c][0], e0);
-        e1 = fmaf(w, v[c][1], e1);
+        e[0] = fmaf(w, v[c][0], e[0]);
+        e[1] = fmaf(w, v[c][1], e[1]);
       }
     }
     // value path: d enc_f = sum_o d_out[o] W[o][3+2l+f]
@@ -434,22 +412,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void n
     for (int c = 0; c < 8; ++c) { gacc[c][0] = de0 * wc[c]; gacc[c][1] = de1 * wc[c]; }
 #pragma unroll
     for (int gd = 0; gd < 3; ++gd) {
-      const int o0 = (gd == 0) ? 1 : 0, o1 = (gd == 2) ? 1 : 2;
       float a0 = 0.f, a1 = 0.f;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        float w = scale;
-        w = w * ((k & 1) ? f[o0] : (1.0f - f[o0]));
-        w = w * ((k & 2) ? f[o1] : (1.0f - f[o1]));
-        const int cl = ((k & 1) << o0) | (((k >> 1) & 1) << o1);
-        const int cr = cl | (1 << gd);
+        const GridD1 t = grid_d1(scale, f, gd, k);
         if constexpr (!AUX) {
-          a0 = fmaf(w, v[cr][0] - v[cl][0], a0);
-          a1 = fmaf(w, v[cr][1] - v[cl][1], a1);
+          a0 = fmaf(t.w, v[t.cr][0] - v[t.cl][0], a0);
+          a1 = fmaf(t.w, v[t.cr][1] - v[t.cl][1], a1);
         }
-        const float s0 = 0.5f * dG[gd] * g0 * w, s1 = 0.5f * dG[gd] * g1 * w;
-        gacc[cr][0] += s0; gacc[cl][0] -= s0;
-        gacc[cr][1] += s1; gacc[cl][1] -= s1;
+        const float s0 = 0.5f * dG[gd] * g0 * t.w, s1 = 0.5f * dG[gd] * g1 * t.w;
+        gacc[t.cr][0] += s0; gacc[t.cl][0] -= s0;
+        gacc[t.cr][1] += s1; gacc[t.cl][1] -= s1;
       }
       if constexpr (AUX) {
         a0 = on ? (float)rec[2 + gd] : 0.0f;
@@ -459,7 +432,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void n
       dy1[gd] = a1;
     }
     {
-      const float l0 = (float)(_Float16)e0 * live, l1 = (float)(_Float16)e1 * live;
+      const float l0 = (float)(_Float16)e[0] * live, l1 = (float)(_Float16)e[1] * live;
       const float v0 = rs * 0.5f * ((dG[0] * dy0[0] + dG[1] * dy0[1]) + dG[2] * dy0[2]);
       const float v1 = rs * 0.5f * ((dG[0] * dy1[0] + dG[1] * dy1[1]) + dG[2] * dy1[2]);
       if (r16) {
@@ -579,17 +552,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void n
       }
     }
     // lin | w0 rows are complete: flush them, then reuse the tile for d_out, d_arg and pts
-    wave_sync_lds();
+    gs_wave_lds_sync();
     tile_flush(tile, 0, 20, A.lin_in, wave_p0, np_all, lane, A.row_stride16);
     tile_flush(tile, 20, 20, A.dw0, wave_p0, np_all, lane, A.row_stride16);
-    wave_sync_lds();
+    gs_wave_lds_sync();
     uint32_t* trow = tile + lane * ROW_TS;
 #pragma unroll
     for (int o = 0; o < 16; ++o) trow[o] = pack2h(dov[2 * o] * rs, dov[2 * o + 1] * rs);
 #pragma unroll
     for (int e = 0; e < 20; ++e) trow[16 + e] = dap[e];
     trow[36] = pack2h(pt[0], pt[1]); trow[37] = pack2h(pt[2], 1.0f); trow[38] = 0u; trow[39] = 0u;   // (x, y, z, 1): the 1 yields column sums
-    wave_sync_lds();
+    gs_wave_lds_sync();
     tile_flush(tile, 0, 16, A.d_out, wave_p0, np_all, lane, A.row_stride16);
     tile_flush(tile, 16, 20, A.d_arg, wave_p0, np_all, lane, A.row_stride16);
     tile_flush(tile, 36, 4, A.pts, wave_p0, np_all, lane, A.row_stride16);
@@ -608,7 +581,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void n
     for (int q = 0; q < 8; ++q) atomicAdd(A.stamp + q, (unsigned long long)t_acc[q]);
 #endif
   // one atomic per workgroup for d inv_s
-  const float ws = gs_wave_sum(d_invs_local);
+  const float ws = gs_wave_sum(h.d_inv_s);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ws;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -634,67 +607,17 @@ __global__ __launch_bounds__(256) void neus_point_raygrad_kernel(BwdArgs A, gs_g
   const int idx = blockIdx.x * 256 + threadIdx.x;
   const int np = A.n * A.s;
   if (idx >= np) return;
-  const int i = idx, ray = i / A.s;
-  const uint8_t mk = A.mask[i];
-  const float dist = A.dists[i], zv = A.z_vals[i], sdf = A.sdf[i];
-  const float d_sdf_in = A.d_sdf[i], da_in = A.d_alpha[i], gerr_ray = A.d_gerr_ray[ray];
-  float g[3], dg_in[3], dir[3], org[3];
+  const int i = idx;
+  PointHead h;
+  point_head(A, i, true, h);
+  const float live = h.live, zm = h.zm;
+  const float (&pt)[3] = h.pt, (&view)[3] = h.view, (&dov)[32] = h.dov, (&ddir)[3] = h.ddir;
+  float dG[3], jac[3];
 #pragma unroll
   for (int d = 0; d < 3; ++d) {
-    g[d] = A.grad[i * 3 + d];
-    dg_in[d] = A.d_grad[i * 3 + d];
-    dir[d] = A.rays_d[ray * 3 + d];
-    org[d] = A.rays_o[ray * 3 + d];
+    jac[d] = h.inside[d] * 2.0f / h.span[d];       // d p / d x (the clamp passes the gradient on [-1, 1])
+    dG[d] = h.dg[d] * jac[d];
   }
-  const float inv_s_ = A.inv_s_dev ? *A.inv_s_dev : A.inv_s;
-  float dxh[40];
-  load_dx40(A, i, 32, dxh);
-  const float live = mk != 0 ? 1.0f : 0.0f;
-  const float zm = zv + dist / 2.0f;
-  float pt[3];
-#pragma unroll
-  for (int d = 0; d < 3; ++d) pt[d] = org[d] + dir[d] * zm;
-  // total dL/dsdf and dL/dg exactly as neus_point_bwd_kernel forms them; plus dL/d dir of the cos term
-  float d_sdf = d_sdf_in * live, dg[3], ddir[3] = {0.f, 0.f, 0.f};
-  const float gn = sqrtf((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]);
-  const float eik = (gn > 0.f) ? gerr_ray * 2.0f * (gn - 1.0f) / gn : 0.0f;
-#pragma unroll
-  for (int d = 0; d < 3; ++d) dg[d] = (dg_in[d] + eik * g[d] + dxh[1 + d]) * live;
-  {
-    const float da = da_in * live;
-    const float cosv = (dir[0] * g[0] + dir[1] * g[1]) + dir[2] * g[2];
-    const float c = -fmaxf(-cosv, 0.0f);
-    const float est_next = sdf + c * dist / 2.0f, est_prev = sdf - c * dist / 2.0f;
-    const float p = 1.0f / (1.0f + expf(-(est_prev * inv_s_)));
-    const float q = 1.0f / (1.0f + expf(-(est_next * inv_s_)));
-    const float raw = (p - q + 1e-5f) / (p + 1e-5f);
-    if (da != 0.0f && raw >= 0.0f && raw <= 1.0f) {
-      const float dp = da * q / ((p + 1e-5f) * (p + 1e-5f));
-      const float dq = -da / (p + 1e-5f);
-      const float dprev = dp * p * (1.0f - p), dnext = dq * q * (1.0f - q);
-      d_sdf += (dprev + dnext) * inv_s_;
-      const float dc = (dnext - dprev) * inv_s_ * dist / 2.0f;
-      if (cosv < 0.0f) {
-#pragma unroll
-        for (int d = 0; d < 3; ++d) { dg[d] += dc * dir[d]; ddir[d] = dc * g[d]; }
-      }
-    }
-  }
-  float view[3], dG[3], jac[3];
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    const float span = A.bound[2 * d + 1] - A.bound[2 * d];
-    float qn = (pt[d] - A.bound[2 * d]) / span * 2.0f - 1.0f;
-    const float inside = (qn >= -1.0f && qn <= 1.0f) ? 1.0f : 0.0f;
-    qn = fminf(fmaxf(qn, -1.0f), 1.0f);
-    view[d] = (qn + 1.0f) / 2.0f;
-    jac[d] = inside * 2.0f / span;                 // d p / d x (the clamp passes the gradient on [-1, 1])
-    dG[d] = dg[d] * jac[d];
-  }
-  float dov[32];
-  dov[0] = d_sdf;
-#pragma unroll
-  for (int o = 1; o < 32; ++o) dov[o] = dxh[4 + (o - 1)] * live;
   float dp[3];                                     // (a) the xyz passthrough columns of the SDF linear layer
 #pragma unroll
   for (int d = 0; d < 3; ++d) {
@@ -706,26 +629,10 @@ __global__ __launch_bounds__(256) void neus_point_raygrad_kernel(BwdArgs A, gs_g
   float dv[3] = {0.f, 0.f, 0.f};                   // dL / d view
 #pragma unroll 1
   for (int l = 0; l < GS_GRID_LEVELS; ++l) {
-    const float scale = m.scale[l];
-    float f[3];
-    uint32_t gi[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      const float pos = fmaf(scale, view[d], 0.5f);
-      const float fl = floorf(pos);
-      gi[d] = (uint32_t)(int)fl;
-      f[d] = pos - fl;
-    }
-    uint32_t cidx[8];
-    grid_corners(m, l, gi, cidx);
-    const size_t off = (size_t)m.offset[l];
-    float v[8][2];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      const uint32_t raw = *reinterpret_cast<const uint32_t*>(A.grid + (off + cidx[c]) * 2);
-      v[c][0] = (float)__builtin_bit_cast(_Float16, (uint16_t)(raw & 0xffffu));
-      v[c][1] = (float)__builtin_bit_cast(_Float16, (uint16_t)(raw >> 16));
-    }
+    uint32_t gi[3], cidx[8];
+    float f[3], v[8][2], dy[3][2];
+    const float scale = grid_cell_gather(m, l, A.grid, view, gi, f, cidx, v);
+    grid_dvalue(scale, f, v, dy);                  // first derivatives d enc / d view (as the backward forms dy)
     float de[2] = {0.f, 0.f};
 #pragma unroll
     for (int o = 0; o < 32; ++o) {
@@ -735,34 +642,21 @@ __global__ __launch_bounds__(256) void neus_point_raygrad_kernel(BwdArgs A, gs_g
     const float gw[2] = {(float)(_Float16)W[3 + 2 * l], (float)(_Float16)W[4 + 2 * l]};
 #pragma unroll
     for (int ft = 0; ft < 2; ++ft) {
-      // first derivatives d enc / d view_gd (as the backward forms dy)
 #pragma unroll
-      for (int gd = 0; gd < 3; ++gd) {
-        const int o0 = (gd == 0) ? 1 : 0, o1 = (gd == 2) ? 1 : 2;
-        float a = 0.f;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          float w = scale;
-          w = w * ((k & 1) ? f[o0] : (1.0f - f[o0]));
-          w = w * ((k & 2) ? f[o1] : (1.0f - f[o1]));
-          const int cl = ((k & 1) << o0) | (((k >> 1) & 1) << o1);
-          a = fmaf(w, v[cl | (1 << gd)][ft] - v[cl][ft], a);
-        }
-        dv[gd] = fmaf(de[ft], a, dv[gd]);
-      }
+      for (int gd = 0; gd < 3; ++gd) dv[gd] = fmaf(de[ft], dy[gd][ft], dv[gd]);
       // mixed second derivatives H[d][e] = scale^2 sum_t w_t (v_11 - v_10 - v_01 + v_00), t the third axis
       float H[3];                                  // H01, H02, H12
 #pragma unroll
       for (int pr = 0; pr < 3; ++pr) {
-        const int d = pr == 2 ? 1 : 0, e = pr == 0 ? 1 : 2, t = 3 - d - e;
-        float h = 0.f;
+        const int d = pr == 2 ? 1 : 0, e = pr == 0 ? 1 : 2;
+        float hs = 0.f;
 #pragma unroll
         for (int bt = 0; bt < 2; ++bt) {
-          const int ct = bt << t;
-          const float x = ((v[ct | (1 << d) | (1 << e)][ft] - v[ct | (1 << d)][ft]) - v[ct | (1 << e)][ft]) + v[ct][ft];
-          h = fmaf(bt ? f[t] : (1.0f - f[t]), x, h);
+          const GridD2 c = grid_d2(d, e, bt);
+          const float x = ((v[c.c11][ft] - v[c.c10][ft]) - v[c.c01][ft]) + v[c.c00][ft];
+          hs = fmaf(bt ? f[c.t] : (1.0f - f[c.t]), x, hs);
         }
-        H[pr] = h * scale * scale;
+        H[pr] = hs * scale * scale;
       }
       const float q = 0.5f * gw[ft];
       dv[0] = fmaf(q, dG[1] * H[0] + dG[2] * H[1], dv[0]);

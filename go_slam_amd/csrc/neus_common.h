@@ -1,7 +1,7 @@
-// Helpers shared by the NeuS kernels (neus.hip, neus_bwd.hip, grid_autograd.hip, render_img.hip): tiny-cuda-nn HashGrid
-// indexing, the wave-merged table-gradient scatter, the per-ray sample placement and the piece layout of a segmented call.
+// Helpers shared by the NeuS kernels (neus.hip, neus_bwd.hip, grid_autograd.hip, render_img.hip): the wave-merged table-gradient scatter, the per-ray sample placement and the piece layout of a segmented call.
 #pragma once
 #include "common.h"
+#include "grid_cell.h"
 #include "../../include/goslam_neus.h"
 
 namespace {
@@ -22,50 +22,29 @@ __device__ __forceinline__ float emb_reduce(float x) {
 __device__ __forceinline__ float emb_sin(float x) { return __builtin_amdgcn_sinf(emb_reduce(x)); }
 __device__ __forceinline__ float emb_cos(float x) { return __builtin_amdgcn_cosf(emb_reduce(x)); }
 
-__device__ __forceinline__ uint32_t grid_index(const gs_grid_meta& m, int l, uint32_t cx, uint32_t cy, uint32_t cz) {
-  const uint32_t size = m.size[l];
-  uint32_t idx;
-  if (m.hashed[l]) {
-    idx = (cx * 1u) ^ (cy * 2654435761u) ^ (cz * 805459861u);
-  } else {
-    const uint32_t res = m.resolution[l];
-    idx = cx + cy * res + cz * res * res;
+// normalized_3d_coordinate (InstantNeuS.py:12-32) with the STATIC bound, clamped to [-1,1]; `view` = the grid's [0,1] input.
+// `inside` (the clamp passes the gradient on [-1, 1]) and `span` make up the Jacobian d p / d x = inside * 2 / span, which
+// every caller applies in its own operation order.
+__device__ __forceinline__ void normalise_point(const float bound[6], const float pt[3], float p[3], float view[3],
+                                                float inside[3], float span[3]) {
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    span[d] = bound[2 * d + 1] - bound[2 * d];
+    float q = (pt[d] - bound[2 * d]) / span[d] * 2.0f - 1.0f;
+    inside[d] = (q >= -1.0f && q <= 1.0f) ? 1.0f : 0.0f;
+    q = fminf(fmaxf(q, -1.0f), 1.0f);
+    p[d] = q;
+    view[d] = (q + 1.0f) / 2.0f;
   }
-  // tcnn: `index % hashmap_size`.  A hashed level holds 2^19 entries (a mask), and a dense level's index is below its
-  // size except at the far corner of the box -- the generic 32-bit modulo (~30 VALU instructions, 8 per level and
-  // point, a third of a level's arithmetic) only runs when it has to.  Same result in every case.
-  if ((size & (size - 1u)) == 0u) return idx & (size - 1u);
-  return idx < size ? idx : idx % size;
 }
 
-// The 8 corner indices of one cell, corner c = (c & 1, (c >> 1) & 1, (c >> 2) & 1) -- the same values as eight
-// grid_index calls (uint32 arithmetic is a ring: (cy + 1) * P == cy * P + P), with the level's kind decided ONCE instead of
-// inside every corner: a hashed level costs 2 multiplications + 2 additions + 12 xors + 8 masks instead of 16
-// multiplications (v_mul_lo_u32 is a quarter-rate instruction) + 16 xors + 8 masks + 12 corner additions and five uniform
-// branches per corner; a dense level is the base index plus the uniform strides 1 / res / res^2.
-__device__ __forceinline__ void grid_corners(const gs_grid_meta& m, int l, const uint32_t (&g)[3], uint32_t (&cidx)[8]) {
-  const uint32_t size = m.size[l];
-  if (m.hashed[l]) {
-    const uint32_t y0 = g[1] * 2654435761u, y1 = y0 + 2654435761u;
-    const uint32_t z0 = g[2] * 805459861u, z1 = z0 + 805459861u;
-    const uint32_t x0 = g[0], x1 = g[0] + 1u;
-    const uint32_t yz[4] = {y0 ^ z0, y1 ^ z0, y0 ^ z1, y1 ^ z1};
-#pragma unroll
-    for (int c = 0; c < 8; ++c) cidx[c] = ((c & 1) ? x1 : x0) ^ yz[c >> 1];
-  } else {
-    const uint32_t res = m.resolution[l], res2 = res * res;
-    const uint32_t base = g[0] + g[1] * res + g[2] * res2;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) cidx[c] = base + (uint32_t)(c & 1) + (((c >> 1) & 1) ? res : 0u) + (((c >> 2) & 1) ? res2 : 0u);
-  }
-  // tcnn: `index % hashmap_size` (see grid_index)
-  if ((size & (size - 1u)) == 0u) {
-#pragma unroll
-    for (int c = 0; c < 8; ++c) cidx[c] &= size - 1u;
-  } else {
-#pragma unroll
-    for (int c = 0; c < 8; ++c) cidx[c] = cidx[c] < size ? cidx[c] : cidx[c] % size;
-  }
+// NeuS (InstantNeuS.py:276-293): the SDF estimates half a step before / behind the sample and their sigmoid CDFs
+__device__ __forceinline__ void neus_cdf_pair(float sdf, float iter_cos, float dist, float inv_s, float& est_prev,
+                                              float& est_next, float& prev_cdf, float& next_cdf) {
+  est_next = sdf + iter_cos * dist / 2.0f;
+  est_prev = sdf - iter_cos * dist / 2.0f;
+  prev_cdf = 1.0f / (1.0f + expf(-(est_prev * inv_s)));
+  next_cdf = 1.0f / (1.0f + expf(-(est_next * inv_s)));
 }
 
 // Scatter one level's 8 corners x 2 features.  Lanes are consecutive samples of a ray, so

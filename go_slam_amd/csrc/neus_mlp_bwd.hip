@@ -35,9 +35,6 @@
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float float16v __attribute__((ext_vector_type(16)));
 typedef __fp16 fp16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
 
 // per-sub-block LDS (halves): X [2][32][32] + [32][16] (later the [32][80] dX staging tile) | TA [2][32][32]: H1, then
@@ -48,12 +45,6 @@ constexpr int NFRAG = 40;          // W1 (10) | W2 (8) | W3^T (2) | W2^T (8) | W
 constexpr int F_W1 = 0, F_W2 = 10, F_W3T = 18, F_W2T = 20, F_W1T = 28;
 constexpr int NPARAM = 64 * 80 + 64 * 64 + 16 * 64;   // 10240, tcnn's layout
 
-__device__ __forceinline__ half8 ld8(const _Float16* p) { return *reinterpret_cast<const half8*>(p); }
-__device__ __forceinline__ void wsync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 __device__ __forceinline__ void zero16(float16v& c) {
 #pragma unroll
   for (int e = 0; e < 16; ++e) c[e] = 0.f;
@@ -293,7 +284,7 @@ void neus_mlp_bwd_kernel(const _Float16* __restrict__ X, const _Float16* __restr
 #pragma unroll
       for (int sb = 0; sb < NSUB; ++sb) cd[sb][mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, bdp[sb], zacc, 0, 0, 0);
     }
-    wsync();
+    gs_wave_lds_sync();
     // ---- dW3 += dpre^T x H2   (K = the 32 points of each sub-block)
 #pragma unroll
     for (int sb = 0; sb < NSUB; ++sb)
@@ -304,7 +295,7 @@ void neus_mlp_bwd_kernel(const _Float16* __restrict__ X, const _Float16* __restr
         for (int nt = 0; nt < 2; ++nt)
           cw3[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, frag32(wb + sb * SUB_LDS + OFF_TB + nt * 1024, kst), cw3[nt], 0, 0, 0);
       }
-    wsync();                                       // dW3 has read H2: TB may be overwritten
+    gs_wave_lds_sync();                                       // dW3 has read H2: TB may be overwritten
     STAMP(2);
     STAMP(3);
     // ---- dH2 = (W3^T dpre) * [H2 > 0] -> B fragments of the next GEMM and TB
@@ -330,7 +321,7 @@ void neus_mlp_bwd_kernel(const _Float16* __restrict__ X, const _Float16* __restr
         cd[sb][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b, cd[sb][1], 0, 0, 0);
       }
     }
-    wsync();
+    gs_wave_lds_sync();
     STAMP(4);
     // ---- dW2 += dH2^T x H1
 #pragma unroll
@@ -347,7 +338,7 @@ void neus_mlp_bwd_kernel(const _Float16* __restrict__ X, const _Float16* __restr
           for (int nt = 0; nt < 2; ++nt) cw2[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, bf[nt], cw2[mt][nt], 0, 0, 0);
         }
       }
-    wsync();                                       // dW2 has read H1: TA may be overwritten
+    gs_wave_lds_sync();                                       // dW2 has read H1: TA may be overwritten
     STAMP(5);
     // ---- dH1 = (W2^T dH2) * [H1 > 0] -> B fragments of the dX GEMM and TA
 #pragma unroll
@@ -373,7 +364,7 @@ void neus_mlp_bwd_kernel(const _Float16* __restrict__ X, const _Float16* __restr
         for (int sb = 0; sb < NSUB; ++sb)
           cx[sb][mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, bfrag(dh[sb][ks >> 1], ks & 1), cx[sb][mt], 0, 0, 0);
       }
-    wsync();
+    gs_wave_lds_sync();
     STAMP(6);
     // ---- dW1 += dH1^T x X
 #pragma unroll
@@ -391,7 +382,7 @@ void neus_mlp_bwd_kernel(const _Float16* __restrict__ X, const _Float16* __restr
           for (int nt = 0; nt < 3; ++nt) cw1[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, bx[nt], cw1[mt][nt], 0, 0, 0);
         }
       }
-    wsync();                                       // dW1 has read X: its tile becomes the [32][80] dX staging tile
+    gs_wave_lds_sync();                                       // dW1 has read X: its tile becomes the [32][80] dX staging tile
     STAMP(7);
 #pragma unroll
     for (int sb = 0; sb < NSUB; ++sb) {
@@ -409,7 +400,7 @@ void neus_mlp_bwd_kernel(const _Float16* __restrict__ X, const _Float16* __restr
           }
         }
     }
-    wsync();
+    gs_wave_lds_sync();
 #pragma unroll
     for (int sb = 0; sb < NSUB; ++sb) {
       const _Float16* XT = wb + sb * SUB_LDS + OFF_X;
@@ -423,7 +414,7 @@ void neus_mlp_bwd_kernel(const _Float16* __restrict__ X, const _Float16* __restr
         *reinterpret_cast<half8*>(dst) = ld8(XT + 8 * idx);
       }
     }
-    wsync();
+    gs_wave_lds_sync();
     STAMP(8);
   };
   if constexpr (DEPTH == 2) {

@@ -1,6 +1,6 @@
 """fp64 restatement of the hash-grid encoding's generic autograd kernels, host only:
 
-  encode      grid_encode_kernel / grid_level (go_slam_amd/csrc/neus.hip, gs_grid_encode): out f16 [n,32], dy_dx f32 [n,32,3]
+  encode      grid_encode_kernel / grid_encode_level (go_slam_amd/csrc/neus.hip, grid_cell.h; gs_grid_encode): out f16 [n,32], dy_dx f32 [n,32,3]
   backward    grid_backward_kernel<SECOND> (go_slam_amd/csrc/grid_autograd.hip, gs_grid_backward): first order (v is None)
               dx and the table gradient; second order (v = d L / d (dx)) ddy, the mixed second derivatives in dx and the
               directional-derivative table gradient
@@ -16,8 +16,8 @@ this module imports: an fp32 operation adds u (|result| + bound) to what its ope
     value before that rounding: the kernel's fp16 lies between the fp16 roundings of the ends of out32's interval.
   * dy_dx: per output dimension gd four fmas of w = (scale wd[o0]) wd[o1] times the corner difference, k = 0..3.  The
     comment in grid_autograd.hip says the backward's dv uses the forward's accumulation order.  Checked against
-    grid_level: both start from w = scale, multiply by the o0 factor, then the o1 factor, take (1 - f) for a clear bit and
-    f for a set bit (grid_level writes the select, the backward indexes wd[d][bit] = {1 - f, f}), use the same cl / cr and
+    grid_dvalue (csrc/grid_cell.h): both start from w = scale, multiply by the o0 factor, then the o1 factor, take (1 - f) for a clear bit and
+    f for a set bit, use the same cl / cr and
     the same two fma chains from 0 -- the same fp32 operations on the same operands, so dv and dy_dx are bit-equal and one
     function (_dv) restates both.
   * dx, first order: a running sum over the 16 levels, in level order, of dy0 dv[d][0] + dy1 dv[d][1]; second order: per
@@ -77,7 +77,7 @@ def _front(meta, l, x, grid16):
 
 
 def _dv(scale, wd, vals):
-    """d y_f / d x_gd of one level, dv[gd][f]: the order of grid_level and of the backward kernel (see the docstring)"""
+    """d y_f / d x_gd of one level, dv[gd][f]: the order of grid_dvalue, which the forward and the backward kernel share (see the docstring)"""
     n = vals.shape[0]
     out = []
     for gd in range(3):

@@ -242,7 +242,7 @@ def ray_bwd(alpha, rgb, z_mid, grad, mask, d_color, d_depth, d_dvar, d_normal, d
 
 # ----------------------------------------------------------------------------------------------- point backward ----
 def grid_corners(meta, l, gi):
-    """csrc/neus_common.h grid_corners: the 8 corner entries (within level l) of the cells gi uint32 [N,3] -> int64 [N,8]
+    """csrc/grid_cell.h grid_corners: the 8 corner entries (within level l) of the cells gi uint32 [N,3] -> int64 [N,8]
     (uint32 arithmetic: dense base + strides, or the xor hash; then `% size`)"""
     M = 0xFFFFFFFF
     g = gi.astype(np.uint64)

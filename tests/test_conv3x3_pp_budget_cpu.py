@@ -2,14 +2,7 @@
 (no GPU needed, nothing is launched) and the code object's kernel metadata is read.  The kernel runs two waves per SIMD,
 so every instantiation has 256 registers (VGPRs + AGPRs) and must not spill: a scratch access in the main loop would also
 break its counted s_waitcnt vmcnt arithmetic."""
-import os
-import re
-import shutil
-import subprocess
-
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from kernel_metadata import kernel_metadata
 
 # (TW, EPI, BN, PROBE) of every instantiation csrc/conv3x3_pp.hip makes; the last one only with -DGS_BUILD_PROBES
 INSTANTIATIONS = [(tw, epi, bn, 0) for tw in (8, 16) for epi, bn in
@@ -17,27 +10,7 @@ INSTANTIATIONS = [(tw, epi, bn, 0) for tw in (8, 16) for epi, bn in
 
 
 def _kernel_metadata(tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        assert not os.path.isdir("/opt/rocm"), "a ROCm installation is present but hipcc was not found"
-        pytest.skip("hipcc not available")
-    csrc = os.path.join(ROOT, "go_slam_amd", "csrc")
-    out = tmp_path / "conv3x3_pp.s"
-    res = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
-                          "-fno-gpu-rdc", "-munsafe-fp-atomics", "-DGS_BUILD_PROBES", "-I", csrc, "-I",
-                          os.path.join(ROOT, "include"), "--cuda-device-only", "-S",
-                          os.path.join(csrc, "conv3x3_pp.hip"), "-o", str(out)],
-                         stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert res.returncode == 0, res.stdout[-2000:]
-    text = open(out).read()
-    meta = text[text.index("amdhsa.kernels:"):]
-    kernels = {}
-    for block in re.split(r"\n  - (?=\.)", meta)[1:]:                    # one YAML list item per kernel
-        field = lambda key: re.search(rf"^\s*\.{key}:\s+(\S+)\s*$", block, re.M)
-        name = field("name").group(1)
-        kernels[name] = {k: int(field(k).group(1)) for k in ("private_segment_fixed_size", "vgpr_count", "agpr_count",
-                                                             "vgpr_spill_count")}
-    return kernels
+    return kernel_metadata("conv3x3_pp.hip", tmp_path, defines=("-DGS_BUILD_PROBES",))
 
 
 def test_every_instantiation_fits_two_waves_per_simd_without_scratch(tmp_path):
