@@ -35,6 +35,11 @@ surfaces onto this one's, `TSDFVolume.merge` fuses another volume into this one,
 of several sessions' volumes, and cfg["tsdf"]["merge"] joins a run's volume with an earlier run's saved one
 (tsdf_merge.py; tests/tsdf_merge_restatement.py).
 
+csrc/tsdf_planes.hip finds what is level: `TSDFVolume.find_planes` returns the volume's dominant planes,
+`tsdf_planes.floor_plane` picks the floor, `TSDFVolume.upright` resamples the volume into a frame that stands on it, and
+cfg["tsdf"]["planes"] / cfg["tsdf"]["upright"] report the planes of a run and hand the navigation keys the upright volume
+(tsdf_planes.py; tests/tsdf_planes_restatement.py).
+
 tsdf_live.py keeps such a volume during a run, while the poses still move; it fuses through
 `keyframe_observations`, the rule `fuse_keyframes` applies per chunk.
 """
@@ -49,6 +54,7 @@ from . import frontier as _frontier
 from . import localize as _localize
 from . import plan as _plan
 from . import tsdf_merge as _merge
+from . import tsdf_planes as _planes
 from . import view as _view
 from .lietorch_shim import SE3
 from .neus.mesh import Mesh, marching_cubes
@@ -272,6 +278,20 @@ class TSDFVolume:
         volume's ([3,4] / [4,4]; None: the identity): see `tsdf_merge.merge_volume`.  Drops the brick flags and returns
         self."""
         return _merge.merge_volume(self, other, T, min_weight)
+
+    def find_planes(self, bins=16, cone_deg=10.0, band=None, max_planes=8, min_cells=64, min_weight=1.0, iterations=3):
+        """The dominant planes of the volume (gs_tsdf_plane_votes / _offsets / _moments), by descending inlier count: a
+        list of {"normal" (unit, toward free space), "offset", "count", "rmse_m", "centroid", "area_m2"}: see
+        `tsdf_planes.find_planes`.  `tsdf_planes.floor_plane` picks the floor among them."""
+        return _planes.find_planes(self, bins, cone_deg, band, max_planes, min_cells, min_weight, iterations)
+
+    def upright(self, plane=None, up_hint=None, up_axis=2, up_sign=+1, heading=None, voxel_size=None, **find_args):
+        """(a new TSDFVolume, T float64 [4,4] world to map): this volume resampled into a frame whose `up_axis` is the
+        normal of `plane` and whose coordinate 0 along it is the plane; plane=None finds the floor under `up_hint`
+        (`find_planes(**find_args)`, `floor_plane`); heading="walls" also lays the largest wall along a lattice axis: see
+        `tsdf_planes.upright_volume`.  The navigation calls (`esdf`, `occupancy_slice`, `plan`, `frontiers`,
+        `next_view`) then take up_axis and heights above the floor."""
+        return _planes.upright_volume(self, plane, up_hint, up_axis, up_sign, heading, voxel_size, **find_args)
 
     def save(self, path):
         """Write the volume as one .npz (tsdf, weight, colors, lo, voxel, trunc, max_weight, dims); `load` gives the same
@@ -947,7 +967,16 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
     earlier run's world: {output}/mesh/tsdf_merged_mesh.ply, {output}/metrics_tsdf_merge.txt (tsdf_merge.merge_text;
     `tsdf_merge_overlap`, `tsdf_merge_rmse_m`, `tsdf_merge_moved_m` and `tsdf_merge_ok` in `stats`) and, with save_volume,
     {output}/mesh/tsdf_merged_volume.npz.  A missing or unreadable file or a bad `init` is refused before anything is
-    fused, a failed registration before anything is written.  Returns the Mesh, or None when the key is absent or
+    fused, a failed registration before anything is written.  With cfg["tsdf"]["planes"] = {enable, bins, cone_deg, band,
+    max_planes, min_cells} (absent by default) the fused volume's dominant planes (TSDFVolume.find_planes) go to
+    {output}/metrics_tsdf_planes.txt (tsdf_planes.planes_text; `tsdf_planes_found` and `tsdf_floor_found` in `stats`), and
+    with cfg["tsdf"]["upright"] = {enable, up_hint, max_tilt_deg, up_axis, up_sign, heading, save_volume} (absent by
+    default; up_hint is a vector or "camera", minus the y column of the first pose of `c2w_list`, the default) the volume
+    is stood upright on its floor (tsdf_planes.floor_plane, TSDFVolume.upright) and the `esdf` key and everything under it
+    runs on the upright volume, in the map frame: `c2w_list` and explicit start and goal points are moved there first,
+    the transform world to map goes to {output}/map/upright.txt (tsdf_planes.transform_text) and, with save_volume, the
+    upright volume to {output}/mesh/tsdf_upright_volume.npz; the mesh, eval_depth, align and merge keep the run's own
+    volume, and a volume without a floor is refused before anything is written.  Returns the Mesh, or None when the key is absent or
     disabled."""
     opt = slam.cfg.get("tsdf") or {}
     if not opt.get("enable", False):
@@ -971,6 +1000,23 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
                              "no sensor depth to align)")
         if stream is None or c2w_list is None:
             raise ValueError("fuse_from_config: tsdf.align needs the stream and its camera-to-world poses")
+    pc, up = opt.get("planes") or {}, opt.get("upright") or {}
+    up_hint = None
+    if pc.get("enable", False) or up.get("enable", False):  # refused before anything is fused or written
+        up_hint = up.get("up_hint", "camera")
+        if isinstance(up_hint, str):
+            if up_hint != "camera":
+                raise ValueError(f"fuse_from_config: tsdf.upright.up_hint is a vector or 'camera' (got {up_hint!r})")
+            if c2w_list is not None and len(c2w_list) > 0:  # a camera's y axis points down
+                up_hint = (-torch.as_tensor(c2w_list[0])[:3, 1]).double().tolist()
+            elif up.get("enable", False):
+                raise ValueError("fuse_from_config: tsdf.upright.up_hint 'camera' needs the run's camera-to-world poses")
+            else:
+                up_hint = None
+        if up_hint is not None:
+            up_hint = _planes._vector3(up_hint, "fuse_from_config: tsdf.upright", "up_hint")
+        if up.get("heading") not in (None, "walls"):
+            raise ValueError(f"fuse_from_config: tsdf.upright.heading must be absent or 'walls' (got {up.get('heading')!r})")
     bound = opt.get("bound") or slam.cfg["mapping"]["bound"]
     min_weight = float(opt.get("min_weight", 1.0))
     vol, mesh = fuse_keyframes(slam.video, bound, float(opt.get("voxel_size", 0.05)), source=opt.get("source", "tracked"),
@@ -983,8 +1029,38 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
         merged = _merge.join_volumes([earlier, vol], [None, merge_init[0]], register=mg.get("register", True),
                                      min_weight=min_weight, levels=mg.get("levels", _merge.DEFAULT_LEVELS),
                                      huber=mg.get("huber", 0.5), min_count=mg.get("min_count", 64))
+    planes = floor = upright = None
+    if pc.get("enable", False) or up.get("enable", False):  # a missing floor is refused before anything is written
+        planes = vol.find_planes(min_weight=min_weight,
+                                 **{k: pc[k] for k in ("bins", "cone_deg", "band", "max_planes", "min_cells") if k in pc})
+        if up_hint is not None:
+            floor = _planes.floor_plane(planes, up_hint, up.get("max_tilt_deg", 35.0))
+        if up.get("enable", False):
+            if floor is None:
+                raise ValueError(f"fuse_from_config: tsdf.upright found no floor among the volume's {len(planes)} planes "
+                                 f"within {up.get('max_tilt_deg', 35.0)} degrees of up_hint {up_hint.tolist()}")
+            upright = _planes.upright_volume(vol, floor, None, up.get("up_axis", 2), up.get("up_sign", 1), up.get("heading"),
+                                             planes=planes)
     os.makedirs(f"{slam.output}/mesh", exist_ok=True)
     mesh.export(f"{slam.output}/mesh/tsdf_mesh.ply")
+    if pc.get("enable", False):
+        with open(f"{slam.output}/metrics_tsdf_planes.txt", "w") as fh:
+            fh.write(_planes.planes_text(planes, floor))
+        if stats is not None:
+            stats.update(tsdf_planes_found=len(planes), tsdf_floor_found=floor is not None)
+        print(f"TSDF planes: {len(planes)} found, floor " + ("none" if floor is None else
+                                                             f"normal {floor['normal'].tolist()!r} offset {floor['offset']!r}"))
+    nav_vol, nav_c2w, nav_point = vol, c2w_list, (lambda point: point)
+    if upright is not None:                                 # the navigation keys below run in the map frame
+        nav_vol, to_map = upright
+        if c2w_list is not None:
+            nav_c2w = _planes.moved_poses(to_map, c2w_list)
+        nav_point = lambda point: point if isinstance(point, str) else _planes.moved_point(to_map, point)  # noqa: E731
+        os.makedirs(f"{slam.output}/map", exist_ok=True)
+        with open(f"{slam.output}/map/upright.txt", "w") as fh:
+            fh.write(_planes.transform_text(to_map))
+        if up.get("save_volume", False):
+            nav_vol.save(f"{slam.output}/mesh/tsdf_upright_volume.npz")
     ev = opt.get("eval_depth") or {}
     if ev.get("enable", False):
         if stream is None or c2w_list is None:
@@ -1000,8 +1076,8 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
     if ed.get("enable", False):
         if c2w_list is None:
             raise ValueError("fuse_from_config: tsdf.esdf needs the run's camera-to-world poses")
-        field = vol.esdf(ed.get("max_distance"), min_weight=min_weight)
-        res = trajectory_clearance(field, c2w_list, out_path=f"{slam.output}/metrics_tsdf_clearance.txt")
+        field = nav_vol.esdf(ed.get("max_distance"), min_weight=min_weight)
+        res = trajectory_clearance(field, nav_c2w, out_path=f"{slam.output}/metrics_tsdf_clearance.txt")
         if stats is not None:
             stats.update(tsdf_clearance_min_m=res["clearance_min_m"], tsdf_clearance_inside=res["n_inside"],
                          tsdf_clearance_unknown=res["n_unknown"])
@@ -1016,11 +1092,11 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
         pl = ed.get("plan") or {}
         if pl.get("enable", False):
             ends = []
-            for end in (pl.get("start", "last"), pl.get("goal", "first")):
-                if end in ("last", "first"):
+            for end in (nav_point(pl.get("start", "last")), nav_point(pl.get("goal", "first"))):
+                if isinstance(end, str) and end in ("last", "first"):
                     if len(c2w_list) == 0:
                         raise ValueError("fuse_from_config: tsdf.esdf.plan needs a camera pose for 'last' / 'first'")
-                    end = torch.as_tensor(c2w_list[-1 if end == "last" else 0])[:3, 3]
+                    end = torch.as_tensor(nav_c2w[-1 if end == "last" else 0])[:3, 3]
                 ends.append(end)
             res = field.plan(ends[0], ends[1], robot_radius=pl.get("robot_radius", 0.0),
                              allow_unknown=pl.get("allow_unknown", False), snap=pl.get("snap", 0.0))
@@ -1033,13 +1109,13 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
                   f"min_clearance_m {res['min_clearance_m']!r}, {int(res['cells'].shape[0])} points")
         fr = ed.get("frontiers") or {}
         if fr.get("enable", False):
-            start = fr.get("start", "last")
+            start = nav_point(fr.get("start", "last"))
             if isinstance(start, str):
                 if start != "last":
                     raise ValueError(f"fuse_from_config: tsdf.esdf.frontiers.start is a world point or 'last' (got {start!r})")
                 if len(c2w_list) == 0:
                     raise ValueError("fuse_from_config: tsdf.esdf.frontiers needs a camera pose for 'last'")
-                start = torch.as_tensor(c2w_list[-1])[:3, 3]
+                start = torch.as_tensor(nav_c2w[-1])[:3, 3]
             res = field.explore(start, robot_radius=fr.get("robot_radius", 0.0), snap=fr.get("snap", 0.0),
                                 min_cells=fr.get("min_cells", 1), order=fr.get("order", "nearest"))
             report = _frontier.summary(res["clusters"], res["cluster"])
@@ -1057,13 +1133,13 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
                   f"chosen {report['cluster']!r}")
         nv = ed.get("next_view") or {}
         if nv.get("enable", False):
-            start = nv.get("start", "last")
+            start = nav_point(nv.get("start", "last"))
             if isinstance(start, str):
                 if start != "last":
                     raise ValueError(f"fuse_from_config: tsdf.esdf.next_view.start is a world point or 'last' (got {start!r})")
                 if len(c2w_list) == 0:
                     raise ValueError("fuse_from_config: tsdf.esdf.next_view needs a camera pose for 'last'")
-                start = torch.as_tensor(c2w_list[-1])[:3, 3]
+                start = torch.as_tensor(nav_c2w[-1])[:3, 3]
             res = field.next_view(start, nv["camera"], nv["up_axis"], nv["height"], n_yaw=nv.get("n_yaw", 8),
                                   robot_radius=nv.get("robot_radius", 0.0), stride=nv.get("stride", 4),
                                   snap=nv.get("snap", 0.0), max_unknown=nv.get("max_unknown", 0),

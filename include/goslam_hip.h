@@ -500,6 +500,61 @@ int gs_tsdf_merge(float* tsdf_d, float* weight_d, float* colors_d, int nx_d, int
                   const float* colors_s, int nx_s, int ny_s, int nz_s, float lo_sx, float lo_sy, float lo_sz,
                   float voxel_s, float trunc_s, const float* d2s, float min_weight, gs_stream_t stream);
 
+/* ---- the dominant planes of that TSDF lattice: a histogram of surface normals, histograms of plane offsets along given
+ *      directions and the moments of the samples near given planes (no counterpart in the reference),
+ *      csrc/tsdf_planes.hip; tests/tsdf_planes_restatement.py restates it ----
+ *
+ * tsdf, weight f32 [nx,ny,nz] as above.  All fp32 and all fp64 arithmetic below is one rounding per operation, no fma; /
+ * is correctly rounded; no square root is taken.  Sizes outside [2, 1024], a NULL pointer, a voxel that is not positive
+ * and finite, a lo, ref or min_weight that is not finite, bins odd or outside [2, 64], n_planes outside [0, 16], n_bins
+ * outside [1, 2048], cos2 outside [0, 1], bin <= 0 or not finite, band < 0 or not finite return GS_ERR_INVALID_ARG before
+ * anything is launched or written.  n_planes == 0 launches nothing.
+ *
+ * The three calls share the surface sample of a cell.  A cell (a, b, c), 0 <= a <= n - 2 per axis, has the eight corners
+ * (a, b, c) + {0,1}^3; cell s = (a * (ny - 1) + b) * (nz - 1) + c.  It is a sample iff (a NaN fails every test)
+ *
+ *     weight >= min_weight at all eight corners
+ *     fabsf(v) < 1.0f for all eight values v, some v < 0 and some v >= 0
+ *     f  = the trilinear value at (0.5, 0.5, 0.5) and g = its gradient there, by gs_tsdf_align_system's lerp sequences
+ *     gg = (g.x * g.x + g.y * g.y) + g.z * g.z ; gg > 0 and f * f <= gg      (the Newton step is at most one voxel)
+ *
+ * and then has the point p = lo + ((float(idx) + 0.5f) - (f / gg) * g) * voxel per axis (t = f / gg once, then t * g per
+ * axis) and the normal direction g, not normalised: it points into free space.
+ *
+ * gs_tsdf_plane_votes: votes u32 [6,bins,bins], zeroed by the caller, receives the cube-map histogram of g over all
+ *   samples (lo and voxel do not enter).  m = the axis of the largest fabsf(g_m), the lowest on a tie; face = 2 m + (g_m <
+ *   0 ? 1 : 0); (u, v) = (g_b / fabsf(g_m), g_c / fabsf(g_m)) for the other two axes b < c; per coordinate the bin is
+ *   min(bins - 1, (int)floorf((u + 1.0f) * float(bins / 2))); votes[face, bin(u), bin(v)] += 1.
+ * gs_tsdf_plane_offsets: normals f64 [n_planes,3] and o0 f64 [n_planes] on the device, each entry rounded to fp32; hist
+ *   u32 [n_planes,n_bins], zeroed by the caller.  A sample agrees with direction n iff d = (n.x * g.x + n.y * g.y) + n.z *
+ *   g.z > 0 and d * d >= cos2 * gg.  For every direction j a sample agrees with: kf = floorf((((n.x * p.x + n.y * p.y) +
+ *   n.z * p.z) - o0[j]) / bin) ; hist[j, (int)kf] += 1 iff 0 <= kf < float(n_bins) (compared as floats).
+ *   Both histograms are sums of integers (fewer than 2^30 cells): the result does not depend on any order.
+ * gs_tsdf_plane_workspace_bytes: n_planes * ceil(cells / chunk) * 16 * 8 with chunk = gs_tsdf_align_chunk and cells = (nx -
+ *   1)(ny - 1)(nz - 1), the chunks' partial rows; 0 for n_planes outside [0, 16] or a size outside [2, 1024].  Needs no GPU.
+ * gs_tsdf_plane_moments: planes f64 [n_planes,4] = (n, o) on the device, each entry rounded to fp32; ref_x, ref_y, ref_z
+ *   a point the moments are taken about; workspace of at least gs_tsdf_plane_workspace_bytes; out f64 [n_planes,16],
+ *   every element written.  Per plane and per sample that agrees with n (as above; agreeing += 1):
+ *
+ *     r = ((n.x * p.x + n.y * p.y) + n.z * p.z) - o ; the sample is an inlier iff fabsf(r) <= band ; inliers += 1
+ *     q = p - ref per axis (fp32), then in fp64: sum_i += q_i ; sum_ij += q_i * q_j for i <= j ; sq += (double)r * (double)r
+ *
+ *   out[j] = sum q (3) at 0, sum q q^T at 3 (00 01 02 11 12 22), sq at 9, inliers at 10, agreeing at 11, 0 at 12 .. 15.
+ *   Order of every fp64 sum, gs_tsdf_align_system's: chunk c holds the cells [c * chunk, (c + 1) * chunk); within it
+ *   thread t of 256 adds its cells t, t + 256, ... in increasing order onto 0.0 (a cell that adds nothing adds nothing),
+ *   a wave adds its 64 partials by v += v[lane ^ m] for m = 32, 16, 8, 4, 2, 1, the four waves' totals are added as ((w0 +
+ *   w1) + w2) + w3, and the chunks' totals in increasing c starting from chunk 0's.  The two counts are integers.  No
+ *   atomics: two runs agree bitwise, and a plane's row does not depend on the other planes of the call.               */
+int gs_tsdf_plane_votes(const float* tsdf, const float* weight, int nx, int ny, int nz, float min_weight, int bins,
+                        unsigned* votes, gs_stream_t stream);
+int gs_tsdf_plane_offsets(const float* tsdf, const float* weight, int nx, int ny, int nz, float lo_x, float lo_y, float lo_z,
+                          float voxel, float min_weight, const double* normals, const double* o0, int n_planes, float cos2,
+                          float bin, int n_bins, unsigned* hist, gs_stream_t stream);
+size_t gs_tsdf_plane_workspace_bytes(int n_planes, int nx, int ny, int nz);
+int gs_tsdf_plane_moments(const float* tsdf, const float* weight, int nx, int ny, int nz, float lo_x, float lo_y, float lo_z,
+                          float voxel, float min_weight, const double* planes, int n_planes, float cos2, float band,
+                          float ref_x, float ref_y, float ref_z, void* workspace, double* out, gs_stream_t stream);
+
 /* ---- Euclidean distance field and 2-D occupancy map of that TSDF lattice (no counterpart in the reference),
  *      csrc/esdf.hip; tests/esdf_restatement.py restates it serially ----
  *
