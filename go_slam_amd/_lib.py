@@ -76,6 +76,9 @@ SIGNATURES = {
     "gs_tsdf_plane_offsets": (c_int, [_P, _P] + [c_int] * 3 + [c_float] * 5 + [_P, _P, c_int, c_float, c_float, c_int, _P, _P]),
     "gs_tsdf_plane_workspace_bytes": (c_size_t, [c_int] * 4),
     "gs_tsdf_plane_moments": (c_int, [_P, _P] + [c_int] * 3 + [c_float] * 5 + [_P, c_int] + [c_float] * 5 + [_P, _P, _P]),
+    "gs_tsdf_object_mark": (c_int, [_P, _P] + [c_int] * 3 + [c_float] * 5 + [_P, c_int, c_float, c_float] + [_P] * 4 + [_P]),
+    "gs_tsdf_object_table": (c_int, [_P, _P] + [c_int] * 3 + [_P, c_size_t, c_int, c_int] + [_P] * 6 + [_P]),
+    "gs_tsdf_object_extents": (c_int, [_P, _P] + [c_int] * 3 + [c_float] * 5 + [_P, _P, c_int, _P, _P, _P]),
     "gs_esdf_build": (c_int, [_P, _P, c_int, c_int, c_int, c_float, c_int, c_float, _P, _P, _P, _P]),
     "gs_esdf_query": (c_int, [_P, _P] + [c_int] * 3 + [c_float] * 4 + [_P, c_int, _P, _P, _P, _P]),
     "gs_esdf_slice": (c_int, [_P] * 3 + [c_int] * 8 + [_P, _P, _P]),

@@ -328,6 +328,12 @@ __device__ __forceinline__ unsigned long long gs_wave_min_u64(unsigned long long
   return v;
 }
 
+__device__ __forceinline__ long long gs_wave_sum_i64(long long v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, GS_WAVE);
+  return v;
+}
+
 __device__ __forceinline__ void gs_atomic_add_f64(double* p, double v) {
   // global_atomic_add_f64 (hardware fp64 atomic on gfx950), relaxed, device scope
   __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

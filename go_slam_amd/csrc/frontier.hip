@@ -16,32 +16,15 @@
 // FR_THREADS * FR_PER cells; emit also clears the row.  frontier_table_kernel passes over the cells once: a frontier
 // cell finds its row by binary search of its label among the roots, the lanes of a wave that share a row reduce their
 // contributions by butterflies, and one lane per (wave, row) issues the integer atomics.  No scratch, no floating point.
-#include "brick_relax.h"
+#include "frontier_rows.h"
 
 namespace {
 
-#ifndef FRONTIER_B0      // the brick; tools/frontier_bench.py measures other shapes through a library built with these set
-#define FRONTIER_B0 4
-#define FRONTIER_B1 4
-#define FRONTIER_B2 32
-#endif
-#ifndef FRONTIER_ROUNDS_MAX   // rounds inside LDS per sweep
-#define FRONTIER_ROUNDS_MAX 64
-#endif
 #ifndef FRONTIER_SHORTCUT     // 0: neighbour relaxation alone (tools/frontier_bench.py counts the sweeps of both)
 #define FRONTIER_SHORTCUT 1
 #endif
-using FrBrick = Brick<FRONTIER_B0, FRONTIER_B1, FRONTIER_B2, FRONTIER_ROUNDS_MAX>;
-constexpr int B0 = FrBrick::B0, B1 = FrBrick::B1, B2 = FrBrick::B2;
-constexpr int FR_THREADS = FrBrick::THREADS;
-constexpr int FR_WAVES = FR_THREADS / GS_WAVE;
-constexpr int FR_MAX = BRICK_MAX_CELLS;                    // cells per axis
-constexpr int FR_PER = 8;                                  // cells per lane of the lattice-wide passes
-constexpr int FR_BLOCK = FR_THREADS * FR_PER;              // cells per workgroup of those passes
 constexpr int FR_SCAN_THREADS = 1024;
 constexpr unsigned FR_NONE = 0xffffffffu;                  // label -1
-
-__device__ __forceinline__ int fr_popc(unsigned long long b) { return __popcll(b); }
 
 // the number of face neighbours of cell p = (c0, c1, c2) that lie inside the lattice and are unknown
 __device__ __forceinline__ int fr_unknown_faces(const unsigned char* __restrict__ state, int p, int c0, int c1, int c2,
@@ -139,32 +122,6 @@ __global__ __launch_bounds__(FR_THREADS) void frontier_relax_kernel(int* label, 
                                                                     int nb2, unsigned char* cur, unsigned char* next,
                                                                     unsigned int* changed) {
   brick_relax<FrBrick>(FrRule{label, (unsigned)(n0 * n1 * n2)}, n0, n1, n2, nb0, nb1, nb2, cur, next, changed);
-}
-
-// Which of this lane's FR_PER cells of block `base` are roots, each one's rank among the block's roots in ascending cell
-// order, and the block's number of roots.  wcount is LDS [FR_PER * FR_WAVES]; holds a barrier.
-__device__ __forceinline__ unsigned fr_rank_roots(const int* __restrict__ label, int ncells, int base, unsigned* wcount,
-                                                  bool (&is)[FR_PER], unsigned (&rank)[FR_PER]) {
-  const int tid = threadIdx.x, lane = tid % GS_WAVE, wave = tid / GS_WAVE;
-#pragma unroll
-  for (int i = 0; i < FR_PER; ++i) {
-    const int p = base + i * FR_THREADS + tid;
-    is[i] = p < ncells && label[p] == p;
-    const unsigned long long b = __ballot(is[i]);
-    rank[i] = fr_popc(b & ((1ull << lane) - 1ull));
-    if (lane == 0) wcount[i * FR_WAVES + wave] = fr_popc(b);
-  }
-  __syncthreads();
-  unsigned run = 0;
-#pragma unroll
-  for (int i = 0; i < FR_PER; ++i) {
-#pragma unroll
-    for (int w = 0; w < FR_WAVES; ++w) {
-      if (w == wave) rank[i] += run;
-      run += wcount[i * FR_WAVES + w];
-    }
-  }
-  return run;
 }
 
 __global__ __launch_bounds__(FR_THREADS) void frontier_count_kernel(const int* __restrict__ label, int ncells,
@@ -298,8 +255,6 @@ __global__ __launch_bounds__(FR_THREADS) void frontier_table_kernel(
   }
 }
 
-int fr_blocks(int n0, int n1, int n2) { return (int)(((long long)n0 * n1 * n2 + FR_BLOCK - 1) / FR_BLOCK); }     // <= 2^19
-
 }  // namespace
 
 extern "C" int gs_frontier_brick(int* b0, int* b1, int* b2) {
@@ -316,7 +271,7 @@ extern "C" size_t gs_frontier_flags_bytes(int n0, int n1, int n2) {
 
 extern "C" size_t gs_frontier_workspace_bytes(int n0, int n1, int n2) {
   if (!brick_dims_ok(n0, n1, n2)) return 0;
-  return 2 * gs_align(sizeof(unsigned) * (size_t)fr_blocks(n0, n1, n2));      // count and first, per block
+  return fr_workspace_bytes(fr_blocks(n0, n1, n2));
 }
 
 extern "C" int gs_frontier_mark(const unsigned char* state, const unsigned char* open, int n0, int n1, int n2,
@@ -361,7 +316,7 @@ extern "C" int gs_frontier_roots(const int* label, int n0, int n1, int n2, void*
   const hipStream_t s = (hipStream_t)stream;
   const int nblk = fr_blocks(n0, n1, n2);
   unsigned* count = (unsigned*)workspace;
-  unsigned* first = (unsigned*)((char*)workspace + gs_align(sizeof(unsigned) * (size_t)nblk));
+  unsigned* first = fr_workspace_first(workspace, nblk);
   GS_TIMING_PRE();
   frontier_count_kernel<<<nblk, FR_THREADS, 0, s>>>(label, n0 * n1 * n2, count);
   GS_CHECK_LAUNCH("frontier_count");
@@ -382,7 +337,7 @@ extern "C" int gs_frontier_table(const unsigned char* state, const int* label, c
   if (rows == 0) return GS_OK;
   const hipStream_t s = (hipStream_t)stream;
   const int nblk = fr_blocks(n0, n1, n2);
-  const unsigned* first = (const unsigned*)((const char*)workspace + gs_align(sizeof(unsigned) * (size_t)nblk));
+  const unsigned* first = fr_workspace_first(workspace, nblk);
   GS_TIMING_PRE();
   frontier_emit_kernel<<<nblk, FR_THREADS, 0, s>>>(label, n0 * n1 * n2, first, rows, root, size, faces,
                                                    (unsigned long long*)sum, bbox, (unsigned long long*)best);

@@ -40,6 +40,10 @@ csrc/tsdf_planes.hip finds what is level: `TSDFVolume.find_planes` returns the v
 cfg["tsdf"]["planes"] / cfg["tsdf"]["upright"] report the planes of a run and hand the navigation keys the upright volume
 (tsdf_planes.py; tests/tsdf_planes_restatement.py).
 
+csrc/tsdf_objects.hip finds what is everything else: `TSDFVolume.find_objects` returns the clusters of surface samples that
+lie on none of the structure planes, each with an oriented box, and cfg["tsdf"]["objects"] writes a run's map/objects.txt
+(tsdf_objects.py; tests/tsdf_objects_restatement.py).
+
 tsdf_live.py keeps such a volume during a run, while the poses still move; it fuses through
 `keyframe_observations`, the rule `fuse_keyframes` applies per chunk.
 """
@@ -54,6 +58,7 @@ from . import frontier as _frontier
 from . import localize as _localize
 from . import plan as _plan
 from . import tsdf_merge as _merge
+from . import tsdf_objects as _objects
 from . import tsdf_planes as _planes
 from . import view as _view
 from .lietorch_shim import SE3
@@ -292,6 +297,12 @@ class TSDFVolume:
         `tsdf_planes.upright_volume`.  The navigation calls (`esdf`, `occupancy_slice`, `plan`, `frontiers`,
         `next_view`) then take up_axis and heights above the floor."""
         return _planes.upright_volume(self, plane, up_hint, up_axis, up_sign, heading, voxel_size, **find_args)
+
+    def find_objects(self, planes, up=None, cone_deg=10.0, band=None, min_cells=16, min_weight=1.0, max_sweeps=65536):
+        """What stands on none of the structure planes `planes` (`tsdf_objects.structure_planes` of `find_planes`' planes):
+        an `Objects` with the object cells' clusters, their table and `.boxes`, one oriented box per cluster of at least
+        min_cells cells (gs_tsdf_object_mark / _table / _extents, gs_frontier_relax): see `tsdf_objects.find_objects`."""
+        return _objects.find_objects(self, planes, up, cone_deg, band, min_cells, min_weight, max_sweeps)
 
     def save(self, path):
         """Write the volume as one .npz (tsdf, weight, colors, lo, voxel, trunc, max_weight, dims); `load` gives the same
@@ -976,7 +987,13 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
     runs on the upright volume, in the map frame: `c2w_list` and explicit start and goal points are moved there first,
     the transform world to map goes to {output}/map/upright.txt (tsdf_planes.transform_text) and, with save_volume, the
     upright volume to {output}/mesh/tsdf_upright_volume.npz; the mesh, eval_depth, align and merge keep the run's own
-    volume, and a volume without a floor is refused before anything is written.  Returns the Mesh, or None when the key is absent or
+    volume, and a volume without a floor is refused before anything is written.  With cfg["tsdf"]["objects"] = {enable,
+    min_area_m2, cone_deg, band, min_cells} (absent by default) what stands on none of the structure planes
+    (tsdf_objects.structure_planes of the planes above -- found here when neither of the two keys is on -- with the floor
+    under up_hint first; TSDFVolume.find_objects on the run's own volume, up the floor's normal, or up_hint when there is
+    no floor) goes to {output}/map/objects.txt in the run's world (tsdf_objects.objects_text; with `upright` a second block
+    in the map frame; `tsdf_objects_found` and `tsdf_objects_on_floor` in `stats`); without an up hint it is refused before
+    anything is fused or written.  Returns the Mesh, or None when the key is absent or
     disabled."""
     opt = slam.cfg.get("tsdf") or {}
     if not opt.get("enable", False):
@@ -1000,9 +1017,9 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
                              "no sensor depth to align)")
         if stream is None or c2w_list is None:
             raise ValueError("fuse_from_config: tsdf.align needs the stream and its camera-to-world poses")
-    pc, up = opt.get("planes") or {}, opt.get("upright") or {}
+    pc, up, ob = opt.get("planes") or {}, opt.get("upright") or {}, opt.get("objects") or {}
     up_hint = None
-    if pc.get("enable", False) or up.get("enable", False):  # refused before anything is fused or written
+    if pc.get("enable", False) or up.get("enable", False) or ob.get("enable", False):  # refused before anything is fused or written
         up_hint = up.get("up_hint", "camera")
         if isinstance(up_hint, str):
             if up_hint != "camera":
@@ -1017,7 +1034,14 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
             up_hint = _planes._vector3(up_hint, "fuse_from_config: tsdf.upright", "up_hint")
         if up.get("heading") not in (None, "walls"):
             raise ValueError(f"fuse_from_config: tsdf.upright.heading must be absent or 'walls' (got {up.get('heading')!r})")
-    bound = opt.get("bound") or slam.cfg["mapping"]["bound"]
+    ob_args = {k: ob[k] for k in ("cone_deg", "band", "min_cells") if k in ob}
+    if ob.get("enable", False):                             # refused before anything is fused or written
+        if up_hint is None:
+            raise ValueError("fuse_from_config: tsdf.objects needs to know where up is: the run's camera-to-world poses or "
+                             "a vector tsdf.upright.up_hint")
+        _objects.find_arguments("fuse_from_config: tsdf.objects", float(opt.get("voxel_size", 0.05)), [], up_hint, **ob_args)
+        _objects.structure_planes([], None, ob.get("min_area_m2", 2.0))
+    bound =opt.get("bound") or slam.cfg["mapping"]["bound"]
     min_weight = float(opt.get("min_weight", 1.0))
     vol, mesh = fuse_keyframes(slam.video, bound, float(opt.get("voxel_size", 0.05)), source=opt.get("source", "tracked"),
                                trunc=opt.get("truncation"), min_weight=min_weight)
@@ -1029,8 +1053,9 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
         merged = _merge.join_volumes([earlier, vol], [None, merge_init[0]], register=mg.get("register", True),
                                      min_weight=min_weight, levels=mg.get("levels", _merge.DEFAULT_LEVELS),
                                      huber=mg.get("huber", 0.5), min_count=mg.get("min_count", 64))
-    planes = floor = upright = None
-    if pc.get("enable", False) or up.get("enable", False):  # a missing floor is refused before anything is written
+    planes = floor = upright = objects = None
+    if pc.get("enable", False) or up.get("enable", False) or ob.get("enable", False):
+        # a missing floor is refused before anything is written
         planes = vol.find_planes(min_weight=min_weight,
                                  **{k: pc[k] for k in ("bins", "cone_deg", "band", "max_planes", "min_cells") if k in pc})
         if up_hint is not None:
@@ -1041,6 +1066,9 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
                                  f"within {up.get('max_tilt_deg', 35.0)} degrees of up_hint {up_hint.tolist()}")
             upright = _planes.upright_volume(vol, floor, None, up.get("up_axis", 2), up.get("up_sign", 1), up.get("heading"),
                                              planes=planes)
+        if ob.get("enable", False):                         # on the run's own volume: resampling loses the floor's samples
+            structure, _ = _objects.structure_planes(planes, floor, ob.get("min_area_m2", 2.0))
+            objects = vol.find_objects(structure, up=up_hint if floor is None else floor, min_weight=min_weight, **ob_args)
     os.makedirs(f"{slam.output}/mesh", exist_ok=True)
     mesh.export(f"{slam.output}/mesh/tsdf_mesh.ply")
     if pc.get("enable", False):
@@ -1061,7 +1089,16 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
             fh.write(_planes.transform_text(to_map))
         if up.get("save_volume", False):
             nav_vol.save(f"{slam.output}/mesh/tsdf_upright_volume.npz")
-    ev = opt.get("eval_depth") or {}
+    if objects is not None:
+        os.makedirs(f"{slam.output}/map", exist_ok=True)
+        with open(f"{slam.output}/map/objects.txt", "w") as fh:
+            fh.write(_objects.objects_text(objects.boxes,
+                                           None if upright is None else _objects.moved_objects(objects, upright[1])))
+        on_floor = 0 if floor is None else sum(1 for b in objects.boxes if 0 in b["touches"])
+        if stats is not None:
+            stats.update(tsdf_objects_found=len(objects.boxes), tsdf_objects_on_floor=on_floor)
+        print(f"TSDF objects: {len(objects.boxes)} found in {objects.n_clusters} clusters, {on_floor} on the floor")
+    ev =opt.get("eval_depth") or {}
     if ev.get("enable", False):
         if stream is None or c2w_list is None:
             raise ValueError("fuse_from_config: tsdf.eval_depth needs the stream and its camera-to-world poses")

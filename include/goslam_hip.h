@@ -707,6 +707,53 @@ int gs_frontier_table(const unsigned char* state, const int* label, const int* c
                       const void* workspace, size_t workspace_bytes, int rows, int capacity, int* root, int* size,
                       int* faces, long long* sum, int* bbox, int* best, gs_stream_t stream);
 
+/* ---- Objects: the surface samples of a TSDF lattice that lie on none of the given structure planes, their clusters and
+ *      one table row per cluster (no counterpart in the reference), csrc/tsdf_objects.hip;
+ *      tests/tsdf_objects_restatement.py restates it ----
+ *
+ * tsdf, weight, the lattice, lo, voxel, min_weight, the surface sample (p, g, gg) of a cell, "agrees" and the fp32
+ * operation order are those of the plane block above (gs_tsdf_plane_*).  The cell lattice is (cx, cy, cz) = (nx - 1, ny -
+ * 1, nz - 1), cell s = (a * cy + b) * cz + c; kind, label and every "cell" below are indexed by s.  Sizes outside [2, 1024]
+ * (cell lattices outside [1, 1024]), a NULL pointer, n_planes outside [0, 16], a voxel that is not positive and finite, a lo
+ * or min_weight that is not finite, cos2 outside [0, 1], band < 0 or not finite, rows < 0 or above capacity, a workspace
+ * that is too small return GS_ERR_INVALID_ARG before anything is launched or written.
+ *
+ * gs_tsdf_object_mark: planes f64 [n_planes,4] = (n, o) on the device, each entry rounded to fp32.  kind u8 [cells] and
+ *   label i32 [cells], every element written; counts u32 [4]; flags as gs_frontier_flags_bytes(cx, cy, cz) sizes them.
+ *     no sample                     kind = 0, label = -1
+ *     for a sample and plane j      r_j = ((n.x * p.x + n.y * p.y) + n.z * p.z) - o ; near_j = fabsf(r_j) <= band ;
+ *                                   on_j = near_j and the sample agrees with n_j
+ *     structure                     some on_j, or near_j for at least two j (a crease between two planes):
+ *                                   kind = 2 + j*, label = -1, j* the lowest j with on_j, else the lowest j with near_j
+ *     otherwise an object cell      kind = 1, label = s
+ *   counts = samples, object cells, structure cells, crease cells (structure without any on_j).  n_planes == 0: every
+ *   sample is an object cell.  Both flag buffers are cleared and the bricks (gs_frontier_brick) that hold an object cell
+ *   marked in buffer 0, as gs_frontier_mark does: gs_frontier_relax(cx, cy, cz, label, flags, ...) and gs_frontier_roots
+ *   run on the result as they are, and the labels' fixed point is the smallest cell index of each 26-connected cluster.
+ * gs_tsdf_object_table: workspace as filled by gs_frontier_roots of these labels; rows, capacity and what is written as
+ *   for gs_frontier_table.  One row per cluster, ascending root:
+ *     root i32 [K], size i32 [K]
+ *     sum i64 [K,3]     the sums of the cells' coordinates (c0, c1, c2); 8-byte aligned
+ *     sum2 i64 [K,6]    the sums of their products 00 01 02 11 12 22; 8-byte aligned.  Below 2^30 * 2^20.
+ *     bbox i32 [K,6]    mins, then maxes
+ *     touch u32 [K]     bit j set iff some cell of the cluster has a 26-neighbour inside the cell lattice with kind == 2 + j
+ *   Integer add, min, max and or: the rows do not depend on any order.
+ * gs_tsdf_object_extents: label at its fixed point, root and rows of the table; axes f64 [rows,3,3] on the device, each
+ *   entry rounded to fp32; ext u32 [rows,3,2], every entry written; rows == 0 launches nothing.  Every cell with label >= 0
+ *   whose label is one of root[0 .. rows) and which is a sample adds t_m = (a.x * p.x + a.y * p.y) + a.z * p.z for the
+ *   three axes a = axes[row, m] of its row: ext[row, m, 0] is the minimum and ext[row, m, 1] the maximum of e(t_m) as
+ *   unsigned integers, e(x) = bits(x) ^ (bits(x) >> 31 ? 0xffffffff : 0x80000000), which orders as the floats do.  A row
+ *   without such a cell holds e(+inf) = 0xff800000 and e(-inf) = 0x007fffff.                                          */
+int gs_tsdf_object_mark(const float* tsdf, const float* weight, int nx, int ny, int nz, float lo_x, float lo_y, float lo_z,
+                        float voxel, float min_weight, const double* planes, int n_planes, float cos2, float band,
+                        unsigned char* kind, int* label, unsigned int* counts, unsigned char* flags, gs_stream_t stream);
+int gs_tsdf_object_table(const unsigned char* kind, const int* label, int cx, int cy, int cz, const void* workspace,
+                         size_t workspace_bytes, int rows, int capacity, int* root, int* size, long long* sum,
+                         long long* sum2, int* bbox, unsigned int* touch, gs_stream_t stream);
+int gs_tsdf_object_extents(const float* tsdf, const float* weight, int nx, int ny, int nz, float lo_x, float lo_y,
+                           float lo_z, float voxel, float min_weight, const int* label, const int* root, int rows,
+                           const double* axes, unsigned int* ext, gs_stream_t stream);
+
 /* ---- View gain: the cells of a state lattice that a camera's rays cross from a candidate pose (no counterpart in the
  *      reference), csrc/view_gain.hip; tests/view_gain_restatement.py restates it serially ----
  *
