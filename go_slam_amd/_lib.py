@@ -94,6 +94,13 @@ SIGNATURES = {
     "gs_frontier_relax": (c_int, [c_int] * 3 + [_P, _P, c_int, c_int, _P, _P]),
     "gs_frontier_roots": (c_int, [_P] + [c_int] * 3 + [_P, c_size_t, _P, _P]),
     "gs_frontier_table": (c_int, [_P, _P, _P] + [c_int] * 3 + [_P, c_size_t, c_int, c_int] + [_P] * 6 + [_P]),
+    "gs_room_mark": (c_int, [_P, _P] + [c_int] * 3 + [_P, _P, _P, _P]),
+    "gs_room_cores": (c_int, [_P] + [c_int] * 3 + [_P, c_size_t, c_int, c_int, _P, _P, _P]),
+    "gs_room_seed": (c_int, [_P] + [c_int] * 3 + [_P, _P, c_int, _P, _P, _P]),
+    "gs_room_relax": (c_int, [_P, _P] + [c_int] * 3 + [_P, _P, c_int, c_int, _P, _P]),
+    "gs_room_door_mark": (c_int, [_P, _P] + [c_int] * 3 + [_P, _P, _P, _P]),
+    "gs_room_table": (c_int, [_P, _P] + [c_int] * 3 + [_P, c_int] + [_P] * 5 + [_P]),
+    "gs_room_door_table": (c_int, [_P] * 4 + [c_int] * 3 + [_P, c_int] + [_P] * 6 + [_P]),
     "gs_view_gain_lds_bytes": (c_size_t, [ctypes.POINTER(c_int)]),
     "gs_view_gain": (c_int, [_P] + [c_int] * 3 + [_P, c_int, _P] + [c_int] * 3 + [ctypes.POINTER(c_int), _P, _P]),
     "gs_frame_prep_color": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P]),

@@ -50,6 +50,42 @@ __device__ __forceinline__ unsigned fr_rank_roots(const int* __restrict__ label,
   return run;
 }
 
+// The pass that folds labelled cells into table rows (tsdf_objects.hip, rooms.hip), over blocks of FR_BLOCK cells: a cell
+// finds its row by binary search of its label among the ascending roots; the lanes of a wave that share a row take one
+// turn together.  Fold: int load(p, id) forms what cell p adds to row id (id < 0: nothing; it may drop the cell by
+// returning -1); fold(row, mine, members, leader) reduces over the lanes with `mine` and has the lane with `leader`
+// issue the atomics.
+template <class Fold>
+__device__ __forceinline__ void fr_fold_rows(const int* __restrict__ label, int ncells, const int* __restrict__ root,
+                                             int rows, Fold& f) {
+  const int tid = threadIdx.x, lane = tid % GS_WAVE;
+  const int base = blockIdx.x * FR_BLOCK;
+  for (int i = 0; i < FR_PER; ++i) {
+    const int p = base + i * FR_THREADS + tid;
+    const int l = p < ncells ? label[p] : -1;
+    if (__ballot(l >= 0) == 0) continue;                    // the wave's 64 cells hold no labelled cell: most do not
+    int id = -1;
+    if (l >= 0) {
+      int lo = 0, hi = rows;                                // the first row whose root is >= l
+      for (int s = 0; s < 31 && lo < hi; ++s) {
+        const int mid = lo + (hi - lo) / 2;
+        if (root[mid] < l) lo = mid + 1; else hi = mid;
+      }
+      if (lo < rows && root[lo] == l) id = lo;              // else: a table that does not hold this cluster
+    }
+    id = f.load(p, id);
+    unsigned long long todo = __ballot(id >= 0);
+    for (int it = 0; it < GS_WAVE && todo != 0; ++it) {     // one turn per distinct row among the wave's cells
+      const int leader = __ffsll((long long)todo) - 1;
+      const int row = __shfl(id, leader, GS_WAVE);
+      const bool mine = id == row;
+      const unsigned long long members = __ballot(mine);
+      todo &= ~members;
+      f.fold(row, mine, members, lane == leader);
+    }
+  }
+}
+
 int fr_blocks(int n0, int n1, int n2) { return (int)(((long long)n0 * n1 * n2 + FR_BLOCK - 1) / FR_BLOCK); }     // <= 2^19
 
 // the workspace: count and first, u32 per block each

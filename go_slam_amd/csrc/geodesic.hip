@@ -10,6 +10,7 @@
 // geodesic_path_kernel is one wave: lanes 0..25 evaluate the moves, a butterfly takes the minimum of (cost + w, move),
 // the steps run serially.  No atomics, no scratch.
 #include "brick_relax.h"
+#include "geo_moves.h"
 
 namespace {
 
@@ -26,24 +27,7 @@ constexpr int B0 = GeoBrick::B0, B1 = GeoBrick::B1, B2 = GeoBrick::B2;
 constexpr int GEO_THREADS = GeoBrick::THREADS;
 constexpr int GEO_INF = GS_GEO_INF;
 
-// move m of 26: its components and weight
-__host__ __device__ constexpr int geo_nb(int m) { return GeoBrick::nb(m); }
-__host__ __device__ constexpr int geo_d0(int m) { return geo_nb(m) / 9 - 1; }
-__host__ __device__ constexpr int geo_d1(int m) { return geo_nb(m) / 3 % 3 - 1; }
-__host__ __device__ constexpr int geo_d2(int m) { return geo_nb(m) % 3 - 1; }
-__host__ __device__ constexpr int geo_weight(int m) {
-  const int nz = (geo_d0(m) != 0) + (geo_d1(m) != 0) + (geo_d2(m) != 0);
-  return nz == 1 ? 1000 : (nz == 2 ? 1414 : 1732);
-}
-// the cells of the box spanned by the centre and move m, as bits of the 3 x 3 x 3 neighbourhood
-__host__ __device__ constexpr unsigned geo_box(int m) {
-  unsigned bits = 0;
-  for (int a = 0; a < 2; ++a)
-    for (int b = 0; b < 2; ++b)
-      for (int c = 0; c < 2; ++c)
-        bits |= 1u << ((a * geo_d0(m) + 1) * 9 + (b * geo_d1(m) + 1) * 3 + (c * geo_d2(m) + 1));
-  return bits;
-}
+static_assert(geo_nb(12) == GeoBrick::nb(12) && geo_nb(13) == GeoBrick::nb(13), "geo_moves.h numbers the moves as the brick");
 
 __global__ __launch_bounds__(GEO_THREADS) void geodesic_fill_kernel(int* __restrict__ cost, long long ncells,
                                                                     unsigned char* __restrict__ flags,

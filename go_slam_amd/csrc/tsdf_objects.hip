@@ -12,8 +12,8 @@
 //   by every lane at the same address (a broadcast).  Writes kind and label, the four counts (ballots per wave, LDS per
 //   workgroup, at most four integer atomics per workgroup) and the dirty byte, in flag buffer 0, of every brick that holds
 //   an object cell.
-// object_rows: the skeleton of the two passes that fold cells into table rows.  A labelled cell finds its row by binary
-//   search of its label among the roots and forms what it adds; the lanes of a wave that share a row reduce by
+// fr_fold_rows (frontier_rows.h): the skeleton of the two passes that fold cells into table rows.  A labelled cell finds
+//   its row by binary search of its label among the roots and forms what it adds; the lanes of a wave that share a row reduce by
 //   butterflies and one lane per (wave, row) issues the integer atomics: add, min, max, or.  Each is exact and commutes,
 //   so the rows do not depend on the order of arrival.
 // tsdf_object_table_kernel: size, the first and second moments of the cell coordinates, the box, and the structure planes
@@ -112,39 +112,6 @@ __device__ __forceinline__ unsigned ob_wave_or(unsigned v) {
   return ob_wave(v, [](unsigned x, unsigned y) { return x | y; });
 }
 
-// Fold: int load(p, id) forms what cell p adds to row id (id < 0: nothing; it may drop the cell by returning -1);
-// fold(row, mine, members, leader) reduces over the lanes with `mine` and has the lane with `leader` issue the atomics.
-template <class Fold>
-__device__ __forceinline__ void object_rows(const int* __restrict__ label, int ncells, const int* __restrict__ root, int rows,
-                                            Fold& f) {
-  const int tid = threadIdx.x, lane = tid % GS_WAVE;
-  const int base = blockIdx.x * FR_BLOCK;
-  for (int i = 0; i < FR_PER; ++i) {
-    const int p = base + i * FR_THREADS + tid;
-    const int l = p < ncells ? label[p] : -1;
-    if (__ballot(l >= 0) == 0) continue;                    // the wave's 64 cells hold no labelled cell: most do not
-    int id = -1;
-    if (l >= 0) {
-      int lo = 0, hi = rows;                                // the first row whose root is >= l
-      for (int s = 0; s < 31 && lo < hi; ++s) {
-        const int mid = lo + (hi - lo) / 2;
-        if (root[mid] < l) lo = mid + 1; else hi = mid;
-      }
-      if (lo < rows && root[lo] == l) id = lo;              // else: a table that does not hold this cluster
-    }
-    id = f.load(p, id);
-    unsigned long long todo = __ballot(id >= 0);
-    for (int it = 0; it < GS_WAVE && todo != 0; ++it) {     // one turn per distinct row among the wave's cells
-      const int leader = __ffsll((long long)todo) - 1;
-      const int row = __shfl(id, leader, GS_WAVE);
-      const bool mine = id == row;
-      const unsigned long long members = __ballot(mine);
-      todo &= ~members;
-      f.fold(row, mine, members, lane == leader);
-    }
-  }
-}
-
 struct TableFold {
   const unsigned char* kind;
   int n0, n1, n2;
@@ -237,7 +204,7 @@ __global__ __launch_bounds__(FR_THREADS) void tsdf_object_emit_kernel(const int*
 
 __global__ __launch_bounds__(FR_THREADS) void tsdf_object_table_kernel(const int* __restrict__ label,
                                                                        const int* __restrict__ root, int rows, TableFold f) {
-  object_rows(label, f.n0 * f.n1 * f.n2, root, rows, f);
+  fr_fold_rows(label, f.n0 * f.n1 * f.n2, root, rows, f);
 }
 
 // e(x): unsigned integers in the order of the floats they encode
@@ -284,7 +251,7 @@ __global__ __launch_bounds__(FR_THREADS) void tsdf_object_extents_init_kernel(un
 __global__ __launch_bounds__(FR_THREADS) void tsdf_object_extents_kernel(const int* __restrict__ label,
                                                                          const int* __restrict__ root, int rows,
                                                                          ExtentFold f) {
-  object_rows(label, f.d.n_cells, root, rows, f);
+  fr_fold_rows(label, f.d.n_cells, root, rows, f);
 }
 
 }  // namespace

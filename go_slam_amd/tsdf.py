@@ -44,6 +44,10 @@ csrc/tsdf_objects.hip finds what is everything else: `TSDFVolume.find_objects` r
 lie on none of the structure planes, each with an oriented box, and cfg["tsdf"]["objects"] writes a run's map/objects.txt
 (tsdf_objects.py; tests/tsdf_objects_restatement.py).
 
+csrc/rooms.hip answers which rooms there are: `ESDF.rooms` splits the space a robot may occupy by clearance into rooms,
+finds the doorways between them and the graph of both, and cfg["tsdf"]["esdf"]["rooms"] writes a run's map/rooms.txt
+(rooms.py; tests/rooms_restatement.py).
+
 tsdf_live.py keeps such a volume during a run, while the poses still move; it fuses through
 `keyframe_observations`, the rule `fuse_keyframes` applies per chunk.
 """
@@ -57,6 +61,7 @@ from . import _lib
 from . import frontier as _frontier
 from . import localize as _localize
 from . import plan as _plan
+from . import rooms as _rooms
 from . import tsdf_merge as _merge
 from . import tsdf_objects as _objects
 from . import tsdf_planes as _planes
@@ -643,6 +648,61 @@ class ESDF:
                    min_clearance_m=float(clearance.item()), goal_cell=goal, cluster=row)
         return out
 
+    def rooms_arguments(self, robot_radius=0.0, core_radius=0.6, min_core_m3=None, min_core_cells=None, max_cost_m=None):
+        """(min_core_cells, max_cost in milli-voxels or None) of `rooms`, or ValueError: radii that are not robot_radius <
+        core_radius <= the field's band, a min_core_m3 that is not positive and finite, a min_core_cells that is no
+        positive integer, both of them given, a max_cost_m out of range (plan_arguments).  Touches no device."""
+        what = "ESDF.rooms"
+        _, _, max_cost = self.plan_arguments([], robot_radius, 0.0, max_cost_m, what)
+        core_radius = float(core_radius)
+        band = self.radius_voxels * self.voxel
+        if not float(robot_radius) < core_radius <= band:
+            raise ValueError(f"{what}: need robot_radius < core_radius <= {band} m, the band of this field (got "
+                             f"{float(robot_radius)} and {core_radius}; build the field with a larger max_distance)")
+        if min_core_m3 is not None and min_core_cells is not None:
+            raise ValueError(f"{what}: give min_core_m3 or min_core_cells, not both")
+        if min_core_m3 is not None:
+            min_core_m3 = float(min_core_m3)
+            if not (min_core_m3 > 0 and math.isfinite(min_core_m3)):
+                raise ValueError(f"{what}: min_core_m3 must be positive and finite (got {min_core_m3})")
+            min_core_cells = max(int(math.ceil(min_core_m3 / self.voxel ** 3)), 1)
+        elif min_core_cells is None:
+            min_core_cells = 1
+        elif isinstance(min_core_cells, bool) or not isinstance(min_core_cells, (int, np.integer)) or \
+                int(min_core_cells) < 1:
+            raise ValueError(f"{what}: min_core_cells must be a positive integer (got {min_core_cells!r})")
+        return int(min_core_cells), max_cost
+
+    @torch.no_grad()
+    def rooms(self, robot_radius=0.0, core_radius=0.6, min_core_m3=None, min_core_cells=None, allow_unknown=False,
+              max_cost_m=None):
+        """Which rooms this field's free space has and which doorways join them: the `rooms.RoomSegments` of `open` =
+        `passable(robot_radius, allow_unknown)`, `core` = `passable(core_radius)` and `d2`.  A place where a ball of
+        `core_radius` fits is the inside of a room; its connected pieces of at least `min_core_cells` cells (or
+        `min_core_m3` cubic metres; default: one cell) seed a room each, and every cell the robot can be at joins the
+        seed it is nearest to along a route, routes longer than `max_cost_m` counting as none.  World-space extras on the
+        result: `.lo`, `.voxel`, `.centroid` float64 [K,3] = lo + centroid_cells * voxel, `.volume_m3` float64 [K] = size *
+        voxel^3, `.box_lo` / `.box_hi` float64 [K,3], the corners of every room's box, and per doorway `.door_centre`
+        float64 [D,3], its widest cell (where a robot passes), `.door_width_m` float64 [D] = 2 * sqrt(widest_d2) * voxel
+        (between the lattice points at the jambs: up to two voxels below the clear opening) and `.door_centroid` float64
+        [D,3].  Host reads: those of `rooms.room_segments`.  ValueError (rooms_arguments)
+        before the device is touched."""
+        min_core_cells, max_cost = self.rooms_arguments(robot_radius, core_radius, min_core_m3, min_core_cells, max_cost_m)
+        out = _rooms.room_segments(self.passable(robot_radius, allow_unknown), self.passable(core_radius), self.d2,
+                                   min_core_cells, max_cost)
+        lo = torch.tensor(self.lo, dtype=torch.float64, device=out.device)[None, :]
+        out.lo, out.voxel = self.lo, self.voxel
+        out.centroid = lo + out.centroid_cells() * self.voxel
+        out.volume_m3 = out.rooms["size"].double() * self.voxel ** 3
+        out.box_lo = lo + out.rooms["bbox"][:, :3].double() * self.voxel
+        out.box_hi = lo + out.rooms["bbox"][:, 3:].double() * self.voxel
+        w = out.doors["widest_cell"].long()
+        n1, n2 = self.dims[1], self.dims[2]
+        out.door_centre = lo + torch.stack([w // (n1 * n2), w // n2 % n1, w % n2], dim=1).double() * self.voxel
+        out.door_width_m = 2.0 * torch.sqrt(out.doors["widest_d2"].double()) * self.voxel
+        out.door_centroid = lo + out.centroid_cells(out.doors) * self.voxel
+        return out
+
     def view_candidates(self, start, up_axis, height, robot_radius=0.0, stride=4, snap=0.0, max_cost_m=None,
                         max_candidates=4096):
         """Where a robot of `robot_radius` could stand to look around: (cells int32 [V,3], cost int32 [V] in milli-voxels,
@@ -964,7 +1024,13 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
     height, n_yaw, robot_radius, stride, snap, start, lam, min_gain_cells, min_solid_cells, max_unknown} (absent by
     default; start is a world point or "last", the default) the pose of ESDF.next_view into {output}/map/next_view.txt
     (view.next_view_text) and, when a view is found, its route into {output}/map/next_view_path.txt (plan.path_text;
-    `tsdf_next_view_found`, `tsdf_next_view_gain_m3` and `tsdf_next_view_candidates` in `stats`).  With
+    `tsdf_next_view_found`, `tsdf_next_view_gain_m3` and `tsdf_next_view_candidates` in `stats`), and with rooms = {enable,
+    robot_radius, core_radius, min_core_m3, snap} (absent by default) the rooms and doorways of ESDF.rooms into
+    {output}/map/rooms.txt (rooms.rooms_text; `tsdf_rooms_found` and `tsdf_doors_found` in `stats`): with tsdf.objects on,
+    the file lists the room of every object (in the map frame when upright), with plan on, the rooms and doorways along
+    map/path.txt, and camera_room is the room of the last camera centre, moved by `snap` metres to a cell the robot may
+    be at; values that are no numbers with 0 <= robot_radius < core_radius (within max_distance), min_core_m3 > 0 and
+    snap >= 0 are refused before anything is fused or written.  With
     cfg["tsdf"]["save_volume"] the fused volume goes to {output}/mesh/tsdf_volume.npz (TSDFVolume.save), and with
     cfg["tsdf"]["align"] = {enable, every, levels, huber, max_depth, min_count} (absent by default; rgbd mode only) every
     `every`-th frame of `stream` is aligned to the fused volume from its pose in `c2w_list` (localize.align_stream, in
@@ -1041,6 +1107,10 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
                              "a vector tsdf.upright.up_hint")
         _objects.find_arguments("fuse_from_config: tsdf.objects", float(opt.get("voxel_size", 0.05)), [], up_hint, **ob_args)
         _objects.structure_planes([], None, ob.get("min_area_m2", 2.0))
+    ed = opt.get("esdf") or {}
+    rm = (ed.get("rooms") or {}) if ed.get("enable", False) else {}
+    if rm.get("enable", False):                             # refused before anything is fused or written
+        rm_args = _rooms.config_arguments(rm, float(opt.get("voxel_size", 0.05)), ed.get("max_distance"))
     bound =opt.get("bound") or slam.cfg["mapping"]["bound"]
     min_weight = float(opt.get("min_weight", 1.0))
     vol, mesh = fuse_keyframes(slam.video, bound, float(opt.get("voxel_size", 0.05)), source=opt.get("source", "tracked"),
@@ -1109,7 +1179,6 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
         if stats is not None:
             stats.update({f"tsdf_{k}": res[k] for k in DEPTH_REPORT_ORDER})
         print("TSDF depth: " + ", ".join(f"{k} {res[k]!r}" for k in DEPTH_REPORT_ORDER))
-    ed = opt.get("esdf") or {}
     if ed.get("enable", False):
         if c2w_list is None:
             raise ValueError("fuse_from_config: tsdf.esdf needs the run's camera-to-world poses")
@@ -1127,6 +1196,7 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
             field.save_map(f"{slam.output}/map", sl["up_axis"], sl["height"], sl.get("robot_radius", 0.0),
                            sl.get("known_fraction", 0.5))
         pl = ed.get("plan") or {}
+        planned = None
         if pl.get("enable", False):
             ends = []
             for end in (nav_point(pl.get("start", "last")), nav_point(pl.get("goal", "first"))):
@@ -1144,6 +1214,7 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
                 stats.update(tsdf_path_reachable=res["reachable"], tsdf_path_length_m=res["length_m"])
             print(f"TSDF path: reachable {res['reachable']!r}, length_m {res['length_m']!r}, "
                   f"min_clearance_m {res['min_clearance_m']!r}, {int(res['cells'].shape[0])} points")
+            planned = res
         fr = ed.get("frontiers") or {}
         if fr.get("enable", False):
             start = nav_point(fr.get("start", "last"))
@@ -1193,6 +1264,24 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
                              tsdf_next_view_candidates=res["n_candidates"])
             print(f"TSDF next view: cell {res['view_cell']!r}, yaw {res['yaw']!r}, gain_m3 {res['gain_m3']!r}, "
                   f"{res['n_candidates']} candidates, {res['n_qualified']} qualified")
+        if rm.get("enable", False):
+            res = field.rooms(robot_radius=rm_args["robot_radius"], core_radius=rm_args["core_radius"],
+                              min_core_m3=rm_args["min_core_m3"])
+            boxes = None
+            if objects is not None:                         # in the frame of the field
+                boxes = objects.boxes if upright is None else _objects.moved_objects(objects, upright[1])
+            here = None
+            if len(c2w_list) > 0:
+                here = _rooms.room_of_point(res, torch.as_tensor(nav_c2w[-1])[:3, 3].double().tolist(), rm_args["snap"])
+            along = res.rooms_along(planned["cells"]) if planned is not None and planned["reachable"] else None
+            report = _rooms.summary(res, boxes, along, here)
+            os.makedirs(f"{slam.output}/map", exist_ok=True)
+            with open(f"{slam.output}/map/rooms.txt", "w") as fh:
+                fh.write(_rooms.rooms_text(report))
+            if stats is not None:
+                stats.update(tsdf_rooms_found=report["n_rooms"], tsdf_doors_found=report["n_doors"])
+            print(f"TSDF rooms: {report['n_rooms']} rooms and {report['n_doors']} doorways over {report['n_open']} open "
+                  f"cells, {report['n_core']} of them core, camera in room {report['camera_room']!r}")
     if opt.get("save_volume", False):
         vol.save(f"{slam.output}/mesh/tsdf_volume.npz")
     if merged is not None:

@@ -754,6 +754,74 @@ int gs_tsdf_object_extents(const float* tsdf, const float* weight, int nx, int n
                            float lo_z, float voxel, float min_weight, const int* label, const int* root, int rows,
                            const double* axes, unsigned int* ext, gs_stream_t stream);
 
+/* ---- Rooms: the free space of a passability lattice split by clearance, the doorways between the parts and one table
+ *      row per room and per doorway (no counterpart in the reference), csrc/rooms.hip; tests/rooms_restatement.py restates
+ *      it serially ----
+ *
+ * The lattice, its linear index p, the 26 moves with weights 1000 / 1414 / 1732, "allowed move" (every cell of the box
+ * the move's two ends span is inside the lattice and open) and GS_GEO_INF are those of the geodesic block above.  open u8:
+ * non-zero where the robot's centre may be.  core u8: non-zero where it has room to spare.  d2 i32 or NULL: the squared
+ * clearance in voxels (gs_esdf_build's d2); NULL and negative values count as 0.  Everything is integer.
+ *
+ * 1. Core cell: open != 0 && core != 0.  Core components: the 26-connected components of the core cells under plain
+ *    adjacency (gs_frontier_relax's rule).  A component's root is its smallest linear index.  A component is kept when the
+ *    caller's keep byte of its row is non-zero (the caller keeps those of at least min_core_cells cells); the cells of a
+ *    dropped component are ordinary open cells from there on.
+ * 2. cost: the gs_geodesic_* field over open seeded at every kept core cell.
+ * 3. Room label R(p): a kept core cell holds its component's root; an open cell with 0 < cost[p] < GS_GEO_INF holds the
+ *    smallest R(p + m) over its parents, the allowed moves m with cost[p + m] + w(m) == cost[p] (at the cost's fixed point
+ *    there is at least one); every other cell holds -1.  Equivalently R(p) is the smallest root among the kept cores whose
+ *    distance to p equals cost[p].  It is the unique fixed point of label[p] = min(label[p], label[p + m]) over parents.
+ * 4. Boundary cell: R(p) >= 0 and some allowed move m with R(p + m) >= 0 and R(p + m) != R(p).
+ * 5. Doorways: the 26-connected components of the boundary cells under plain adjacency; door_label i32: -1 off them, else
+ *    the component's smallest linear index.
+ * 6. Room table, one row per kept core by ascending root, the row number is the room's id:
+ *      root i32 [K], size i32 [K] (cells with R == root), core_size i32 [K] (those of them with cost 0: the kept core),
+ *      sum i64 [K,3] (8-byte aligned), bbox i32 [K,6] (mins, then maxes), reach i32 [K] (the largest cost in the room)
+ * 7. Door table, one row per doorway by ascending root:
+ *      root, size, sum, bbox as above over the doorway's cells
+ *      room_lo, room_hi i32 [D]   the smallest and largest label found on the doorway's cells and across their allowed
+ *                                 moves to a differing label (at a junction of three rooms: only the extremes)
+ *      widest u64 [D]             8-byte aligned; the maximum over the doorway's cells of (d2 << 32) | (0xffffffff - p):
+ *                                 the cell with the largest d2, ties to the lowest index
+ *
+ * Sizes outside [1, 1024], a NULL pointer where one is needed, rows < 0 or above capacity, a workspace that is too small
+ * or a misaligned 64-bit column return GS_ERR_INVALID_ARG before anything is launched or written.  Every entry enqueues
+ * on the stream and reads nothing back.  flags are gs_frontier_flags_bytes' two buffers (the brick is gs_frontier_brick's),
+ * the workspace is gs_frontier_workspace_bytes'.
+ *
+ * gs_room_mark: label = own index on a core cell, -1 elsewhere, every element written; counts u32 [2] = open cells, core
+ *   cells; both flag buffers cleared, then the bricks that hold a core cell marked in buffer 0: gs_frontier_relax and
+ *   gs_frontier_roots run on the result as they are.
+ * gs_room_cores: workspace as filled by gs_frontier_roots of `label` at its fixed point, rows = its K.  root [rows]
+ *   ascending and size [rows] (or NULL: not wanted), the components' numbers of cells.  rows == 0 launches nothing.
+ *   (Any label lattice of gs_frontier_relax serves: the doorways' too.)
+ * gs_room_seed: root, keep u8 [rows]; label = -1 on every cell whose label is no root with a non-zero keep byte; both flag
+ *   buffers cleared, then every brick that holds an open cell marked in buffer 0, which contains every brick in which
+ *   a cell can be the first to take a label.
+ * gs_room_relax: cost at its fixed point over `open` seeded at the cells label >= 0; sweep0, k, the flag buffers and
+ *   changed as for gs_geodesic_relax, with "label" for "cell".
+ * gs_room_door_mark: label at gs_room_relax's fixed point; door_label = own index on a boundary cell, -1 elsewhere, every
+ *   element written; count u32 [1] = boundary cells; flags as gs_room_mark leaves them, for the boundary cells.
+ * gs_room_table / gs_room_door_table: root [rows] ascending, as gs_room_cores wrote it (for the rooms: its kept rows);
+ *   rows [0, rows) of every other column are written; rows == 0 launches nothing.  Integer add, min and max: the rows do
+ *   not depend on any order.                                                                                           */
+int gs_room_mark(const unsigned char* open, const unsigned char* core, int n0, int n1, int n2, int* label,
+                 unsigned int* counts, unsigned char* flags, gs_stream_t stream);
+int gs_room_cores(const int* label, int n0, int n1, int n2, const void* workspace, size_t workspace_bytes, int rows,
+                  int capacity, int* root, int* size, gs_stream_t stream);
+int gs_room_seed(const unsigned char* open, int n0, int n1, int n2, const int* root, const unsigned char* keep, int rows,
+                 int* label, unsigned char* flags, gs_stream_t stream);
+int gs_room_relax(const unsigned char* open, const int* cost, int n0, int n1, int n2, int* label, unsigned char* flags,
+                  int sweep0, int k, unsigned int* changed, gs_stream_t stream);
+int gs_room_door_mark(const unsigned char* open, const int* label, int n0, int n1, int n2, int* door_label,
+                      unsigned int* count, unsigned char* flags, gs_stream_t stream);
+int gs_room_table(const int* label, const int* cost, int n0, int n1, int n2, const int* root, int rows, int* size,
+                  int* core_size, long long* sum, int* bbox, int* reach, gs_stream_t stream);
+int gs_room_door_table(const unsigned char* open, const int* label, const int* door_label, const int* d2, int n0, int n1,
+                       int n2, const int* root, int rows, int* size, long long* sum, int* bbox, int* room_lo, int* room_hi,
+                       unsigned long long* widest, gs_stream_t stream);
+
 /* ---- View gain: the cells of a state lattice that a camera's rays cross from a candidate pose (no counterpart in the
  *      reference), csrc/view_gain.hip; tests/view_gain_restatement.py restates it serially ----
  *
