@@ -101,6 +101,10 @@ SIGNATURES = {
     "gs_room_door_mark": (c_int, [_P, _P] + [c_int] * 3 + [_P, _P, _P, _P]),
     "gs_room_table": (c_int, [_P, _P] + [c_int] * 3 + [_P, c_int] + [_P] * 5 + [_P]),
     "gs_room_door_table": (c_int, [_P] * 4 + [c_int] * 3 + [_P, c_int] + [_P] * 6 + [_P]),
+    "gs_segment_sight": (c_int, [_P] + [c_int] * 3 + [_P, c_int, _P, _P]),
+    "gs_segment_min": (c_int, [_P] + [c_int] * 3 + [_P, c_int, _P, _P, _P]),
+    "gs_path_sight": (c_int, [_P] + [c_int] * 3 + [_P, c_int, c_int, _P, _P]),
+    "gs_path_shortcut": (c_int, [_P, _P, c_int, c_int, _P, _P, _P, _P]),
     "gs_view_gain_lds_bytes": (c_size_t, [ctypes.POINTER(c_int)]),
     "gs_view_gain": (c_int, [_P] + [c_int] * 3 + [_P, c_int, _P] + [c_int] * 3 + [ctypes.POINTER(c_int), _P, _P]),
     "gs_frame_prep_color": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P]),

@@ -6,6 +6,12 @@ cell down to a seed.  The field is integer and the unique fixed point of its rel
 bit for bit (tests/geodesic_restatement.py; include/goslam_hip.h, gs_geodesic_*).
 `ESDF.passable` / `plan` / `reachable` (tsdf.py) put a fused volume's distance field under it, `plan_on_map` a 2-D
 occupancy map, and `path_text` / `parse_path` are the run's map/path.txt.
+
+`line_of_sight`, `segment_min` and `straighten` (csrc/sight.hip; include/goslam_hip.h, gs_segment_* / gs_path_*;
+tests/sight_restatement.py) turn such a chain of lattice cells into the few waypoints a controller
+wants: the shortest route over the path's own cells whose straight legs the robot may take.  `with_waypoints` is the one
+helper behind the `straighten=True` of `ESDF.plan`, `explore`, `next_view` and `plan_on_map`, and `straight_path_text` /
+`parse_straight_path` are the run's map/path_straight.txt.
 """
 import ctypes
 import math
@@ -20,6 +26,8 @@ MAX_COST = INF - 1732                  # GS_GEO_MAX_COST
 MAX_CELLS = 1024                       # per axis
 SWEEP_BATCH = 8                        # sweeps enqueued per host read of `changed`
 MAP_FREE, MAP_UNKNOWN = 254, 205       # tsdf.MAP_FREE, tsdf.MAP_UNKNOWN
+PATH_MAX_CELLS = 16384                 # GS_PATH_MAX_CELLS
+DEFAULT_WINDOW = 256                   # earlier cells a path cell is tested against
 
 
 def _cell(cell, dims, what):
@@ -203,15 +211,19 @@ def map_cell(shape, origin, res, xy, name, what):
 
 
 @torch.no_grad()
-def plan_on_map(grid, start_xy, goal_xy, allow_unknown=False):
+def plan_on_map(grid, start_xy, goal_xy, allow_unknown=False, straighten=False, window=DEFAULT_WINDOW):
     """Plan on the 2-D map `grid` (the dict of `ESDF.occupancy_slice` or `load_map`: cells uint8 [n_u,n_v], origin,
     resolution) from `start_xy` to `goal_xy` (map coordinates along the two image axes).  A cell passes when it is free
     (254), with `allow_unknown` also when unknown (205); the lattice is [1,n_u,n_v]; a point's cell is
     floor((xy - origin) / resolution).  -> {"reachable", "cells": int32 [L,2] (u, v) start to goal on the device,
     "points": float64 [L,2], their centres origin + (cell + 0.5) * resolution, "length_m", "start_cell", "goal_cell",
-    "sweeps"}; unreachable: L = 0 and length_m inf.  ValueError for a point outside the map, before the device is
+    "sweeps"}; unreachable: L = 0 and length_m inf.  With `straighten` the dict gains `with_waypoints`' keys
+    ("waypoint_index", "waypoints" int32 [K,2], "waypoint_points" float64 [K,2], "straight_length_m": the shortest route
+    over the path's own cells by straight legs across passable cells, each cell tested against the `window` before it);
+    without it nothing else is launched.  ValueError for a point outside the map or a bad window, before the device is
     touched."""
     what = "plan_on_map"
+    window = _window(window, what)
     cells = grid["cells"]
     cells = cells if isinstance(cells, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(cells))
     if cells.dim() != 2 or cells.dtype != torch.uint8:
@@ -230,8 +242,242 @@ def plan_on_map(grid, start_xy, goal_xy, allow_unknown=False):
     reachable = int(path.shape[0]) > 0
     length = float(field.cost[0, ends[0][0], ends[0][1]].item()) * res / 1000.0 if reachable else math.inf
     points = torch.tensor(origin, dtype=torch.float64, device=path.device)[None, :] + (path.double() + 0.5) * res
-    return {"reachable": reachable, "cells": path, "points": points, "length_m": length, "start_cell": ends[0],
-            "goal_cell": ends[1], "sweeps": field.sweeps}
+    out = {"reachable": reachable, "cells": path, "points": points, "length_m": length, "start_cell": ends[0],
+           "goal_cell": ends[1], "sweeps": field.sweeps}
+    if straighten:
+        corner = torch.tensor(origin, dtype=torch.float64, device=path.device)[None, :]
+        out = with_waypoints(out, field.passable, window, lambda c: corner + (c.double() + 0.5) * res, res, what=what)
+    return out
+
+
+# ---- line of sight and the shortest shortcut of a path (csrc/sight.hip) ---------------------------------------------------
+def _sight_lattice(t, name, dtypes, what):
+    """dims of the lattice tensor `t`, or ValueError."""
+    if not isinstance(t, torch.Tensor) or t.dtype not in dtypes:
+        raise ValueError(f"{what}: {name} must be a tensor of {' or '.join(str(d).replace('torch.', '') for d in dtypes)} "
+                         f"(got {getattr(t, 'dtype', type(t).__name__)})")
+    if t.dim() != 3 or not all(1 <= int(n) <= MAX_CELLS for n in t.shape):
+        raise ValueError(f"{what}: {name} must be [n0,n1,n2] with every size in [1, {MAX_CELLS}] (got {list(t.shape)}); "
+                         "a 2-D map [n_u,n_v] is the lattice [1,n_u,n_v]")
+    return tuple(int(n) for n in t.shape)
+
+
+def _cell_rows(cells, name, what):
+    """`cells` (a tensor or anything numpy reads) as it is when an integer tensor [n,3], else as an int32 host tensor
+    [n,3]; ValueError for another shape or for numbers that are no integers.  Touches no device."""
+    if isinstance(cells, torch.Tensor):
+        if cells.dim() != 2 or cells.shape[1] != 3 or cells.dtype not in (torch.int32, torch.int64, torch.int16, torch.uint8):
+            raise ValueError(f"{what}: {name} must be integers [n,3] (got {cells.dtype} {list(cells.shape)})")
+        return cells
+    c = np.asarray(cells)
+    if c.size == 0:
+        c = np.zeros((0, 3), dtype=np.int32)
+    if c.ndim != 2 or c.shape[1] != 3 or not np.issubdtype(c.dtype, np.integer):
+        raise ValueError(f"{what}: {name} must be integers [n,3] (got {c.dtype} {list(c.shape)})")
+    if c.size and (c.min() < -2 ** 31 or c.max() >= 2 ** 31):
+        raise ValueError(f"{what}: {name} must be integers that fit 32 bits")
+    return torch.from_numpy(np.ascontiguousarray(c, dtype=np.int32))
+
+
+def _segments(lattice, a, b, what):
+    """(the lattice on the GPU, segs int32 [n,6] beside it) for the cells `a` and `b` [n,3]."""
+    a, b = _cell_rows(a, "a", what), _cell_rows(b, "b", what)
+    if a.shape != b.shape:
+        raise ValueError(f"{what}: a is {list(a.shape)} and b is {list(b.shape)}")
+    dev = lattice.device if lattice.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    segs = torch.cat([a.to(device=dev, dtype=torch.int32), b.to(device=dev, dtype=torch.int32)], dim=1).contiguous()
+    return lattice.to(dev), segs
+
+
+@torch.no_grad()
+def line_of_sight(passable, a, b):
+    """bool [n] on the device: whether the cell a[i] sees the cell b[i] over `passable` (uint8 or bool [n0,n1,n2]; on the
+    GPU, or moved there), i.e. both lie inside the lattice and every cell whose closed unit cube the straight segment
+    between the two centres meets is passable (gs_segment_sight): a robot whose centre may be at the passable cells may go
+    straight from a to b.  `a`, `b`: integers [n,3], tensors or arrays; a cell outside the lattice sees nothing.  One
+    launch, nothing is read back.  ValueError for bad shapes or dtypes before the device is touched."""
+    what = "line_of_sight"
+    dims = _sight_lattice(passable, "passable", (torch.uint8, torch.bool), what)
+    passable, segs = _segments(passable, a, b, what)
+    passable = passable.to(torch.uint8).contiguous()
+    n = int(segs.shape[0])
+    out = torch.empty(n, dtype=torch.uint8, device=segs.device)
+    with torch.cuda.device(segs.device):
+        _lib.check(_lib.lib().gs_segment_sight(_lib.ptr(passable), *dims, _lib.ptr(segs), n, _lib.ptr(out),
+                                               _lib.stream_ptr(segs.device)), what)
+    return out != 0
+
+
+@torch.no_grad()
+def segment_min(field, a, b):
+    """(value int32 [n], cell int32 [n]) on the device: the smallest value of `field` (int32 [n0,n1,n2]; on the GPU, or
+    moved there) over the cells the straight segment from a[i] to b[i] meets (`line_of_sight`'s cells) and the lowest
+    linear index that holds it (gs_segment_min); INT32_MIN and -1 when an end lies outside the lattice.  With ESDF.d2 as
+    the field it is the squared clearance of a straight leg.  One launch, nothing is read back."""
+    what = "segment_min"
+    dims = _sight_lattice(field, "field", (torch.int32,), what)
+    field, segs = _segments(field, a, b, what)
+    field = field.contiguous()
+    n = int(segs.shape[0])
+    value = torch.empty(n, dtype=torch.int32, device=segs.device)
+    cell = torch.empty(n, dtype=torch.int32, device=segs.device)
+    with torch.cuda.device(segs.device):
+        _lib.check(_lib.lib().gs_segment_min(_lib.ptr(field), *dims, _lib.ptr(segs), n, _lib.ptr(value), _lib.ptr(cell),
+                                             _lib.stream_ptr(segs.device)), what)
+    return value, cell
+
+
+def _window(window, what):
+    if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or int(window) < 1:
+        raise ValueError(f"{what}: window must be a positive integer (got {window!r})")
+    return int(window)
+
+
+def straighten_arguments(passable, cells, window=DEFAULT_WINDOW, what="straighten"):
+    """(dims, cells as `_cell_rows` gives them, window) of `straighten`, or ValueError.  Touches no device."""
+    dims = _sight_lattice(passable, "passable", (torch.uint8, torch.bool), what)
+    cells = _cell_rows(cells, "cells", what)
+    if int(cells.shape[0]) < 1:
+        raise ValueError(f"{what}: a path has at least one cell (got {list(cells.shape)})")
+    return dims, cells, _window(window, what)
+
+
+@torch.no_grad()
+def straighten(passable, cells, window=DEFAULT_WINDOW):
+    """The shortest route from the first to the last of the path's `cells` (integers [L,3], L >= 1) that stops only at
+    cells of the path and whose every straight leg the robot may take (`line_of_sight` over `passable`): each cell is
+    tested against the `window` cells before it (gs_path_sight; the window is cut to L - 1) and a dynamic programme
+    picks the stops (gs_path_shortcut; equal lengths go to the earlier stop).  -> {"index": int32 [K], the kept cells'
+    positions in the path, ascending, 0 and L - 1 always among them, "cells": int32 [K,3], both on the device, "length":
+    the route's length in milli-voxels (a leg is floor(1000 * its Euclidean length in cells)), "window": the window
+    used}.  A lattice path's own moves see, so the result is never longer than the path and `window` = 1 returns the path.
+    A path of more than PATH_MAX_CELLS = 16384 cells is straightened in consecutive pieces of that many cells that share
+    an end cell, which is kept: a limit, since no leg spans two pieces.  One read per piece: K and the length together.
+    ValueError before the device is touched; RuntimeError when the last cell cannot be reached, that is when some cell
+    sees none of the `window` before it (a path through blocked cells)."""
+    what = "straighten"
+    dims, cells, window = straighten_arguments(passable, cells, window, what)
+    L_all = int(cells.shape[0])
+    L = _lib.lib()
+    dev = passable.device if passable.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    passable = passable.to(device=dev, dtype=torch.uint8).contiguous()
+    cells = cells.to(device=dev, dtype=torch.int32).contiguous()
+    kept, length, used = [], 0, 1
+    with torch.cuda.device(dev):
+        stream = _lib.stream_ptr(dev)
+        for first in range(0, max(L_all - 1, 1), PATH_MAX_CELLS - 1):
+            piece = cells[first:first + PATH_MAX_CELLS]
+            n = int(piece.shape[0])
+            w = max(min(window, n - 1), 1)
+            used = max(used, w)
+            sight = torch.empty((n, (w + 63) // 64), dtype=torch.int64, device=dev)             # u64 words
+            index = torch.empty(n, dtype=torch.int32, device=dev)
+            tail = torch.empty(2, dtype=torch.int32, device=dev)                                 # n_out, length
+            _lib.check(L.gs_path_sight(_lib.ptr(passable), *dims, _lib.ptr(piece), n, w, _lib.ptr(sight), stream),
+                       f"{what} (sight)")
+            _lib.check(L.gs_path_shortcut(_lib.ptr(sight), _lib.ptr(piece), n, w, _lib.ptr(index), _lib.ptr(tail[0:]),
+                                          _lib.ptr(tail[1:]), stream), f"{what} (shortcut)")
+            k, piece_length = tail.cpu().tolist()                                                # the piece's one read
+            if k < 0:
+                raise RuntimeError(f"{what}: cell {first + n - 1} of the path cannot be reached from cell {first} with a "
+                                   f"window of {w}: some cell in between sees none of the {w} before it")
+            kept.append(index[0 if first == 0 else 1:k] + first)
+            length += piece_length
+    index = kept[0] if len(kept) == 1 else torch.cat(kept)
+    return {"index": index, "cells": cells[index.long()], "length": length, "window": used}
+
+
+@torch.no_grad()
+def with_waypoints(route, passable, window, to_points, metres_per_cell, d2=None, dist=None, what="straighten"):
+    """`route` (the dict of `ESDF.plan` or `plan_on_map`; not changed) with the keys of its straightened form added:
+    "waypoint_index" int32 [K] and "waypoints", the kept cells (as `cells` has them: [K,3], or [K,2] on a map), on the
+    device, "waypoint_points" float64 = to_points(waypoints), "straight_length_m" = the straightened length *
+    metres_per_cell / 1000, and with `d2` and `dist` (the ESDF's) "straight_min_clearance_m": `dist` at the cell that
+    `segment_min` reports for `d2` over the kept legs, the smallest of them, ties to the lowest linear index.  An
+    unreachable route gets empty waypoints, inf and nan.  Reads: `straighten`'s, and one for the clearance."""
+    cells = route["cells"]
+    out = dict(route)
+    if not isinstance(cells, torch.Tensor) or cells.dim() != 2 or cells.shape[1] not in (2, 3):
+        raise ValueError(f"{what}: a route's cells are [L,3] or [L,2] (got {getattr(cells, 'shape', cells)!r})")
+    flat = int(cells.shape[1]) == 2
+    window = _window(window, what)
+    if int(cells.shape[0]) == 0:
+        out.update(waypoint_index=torch.zeros(0, dtype=torch.int32, device=cells.device), waypoints=cells[:0],
+                   waypoint_points=to_points(cells[:0]), straight_length_m=math.inf)
+        if d2 is not None:
+            out["straight_min_clearance_m"] = math.nan
+        return out
+    cells3 = torch.cat([torch.zeros_like(cells[:, :1]), cells], dim=1) if flat else cells
+    res = straighten(passable, cells3, window)
+    way = res["cells"][:, 1:].contiguous() if flat else res["cells"]
+    out.update(waypoint_index=res["index"], waypoints=way, waypoint_points=to_points(way),
+               straight_length_m=res["length"] * metres_per_cell / 1000.0)
+    if d2 is not None:
+        legs = res["cells"]
+        value, cell = segment_min(d2, legs[:-1] if len(legs) > 1 else legs, legs[1:] if len(legs) > 1 else legs)
+        worst = int((value.long() * (1 << 32) + cell.long()).min().item()) & 0xffffffff          # one read
+        out["straight_min_clearance_m"] = float(dist.reshape(-1)[worst].item())
+    return out
+
+
+STRAIGHT_REPORT_ORDER = ("reachable", "length_m", "min_clearance_m", "n_points", "lattice_length_m", "n_lattice_points")
+_STRAIGHT_HEADER = "Straightened collision-free path"
+
+
+def straight_path_text(result):
+    """The text of map/path_straight.txt for the dict of `ESDF.plan(..., straighten=True)`: `path_text`'s layout with a
+    header of its own -- two header lines, `name<TAB>repr(value)` for reachable, length_m (the straightened length),
+    min_clearance_m (along the straight legs), n_points, lattice_length_m and n_lattice_points (the lattice route's), then
+    one `x y z` line per waypoint with repr(): reading the file gives back the numbers bit for bit."""
+    pts = result["waypoint_points"]
+    pts = pts.detach().cpu().numpy() if isinstance(pts, torch.Tensor) else np.asarray(pts)
+    pts = np.asarray(pts, dtype=np.float64).reshape(-1, 3)
+    head = {"reachable": bool(result["reachable"]), "length_m": float(result["straight_length_m"]),
+            "min_clearance_m": float(result["straight_min_clearance_m"]), "n_points": int(pts.shape[0]),
+            "lattice_length_m": float(result["length_m"]), "n_lattice_points": int(result["cells"].shape[0])}
+    lines = [_STRAIGHT_HEADER + " through the fused TSDF volume's distance field, start to goal: the waypoints [m], cells "
+             "of the lattice route of map/path.txt joined by straight legs that keep the robot's radius from every surface",
+             "(length_m: the legs' length; min_clearance_m: the smallest distance to a surface along them; "
+             "lattice_length_m, n_lattice_points: the lattice route's; inf and nan when the goal cannot be reached; then per "
+             "waypoint: x y z)"]
+    lines += [f"{k}\t{head[k]!r}" for k in STRAIGHT_REPORT_ORDER]
+    lines += [f"{float(p[0])!r} {float(p[1])!r} {float(p[2])!r}" for p in pts]
+    return "\n".join(lines) + "\n"
+
+
+def parse_straight_path(text):
+    """straight_path_text's inverse: (the dict of STRAIGHT_REPORT_ORDER, waypoints float64 [n,3])."""
+    lines = text.splitlines()
+    if len(lines) < 2 + len(STRAIGHT_REPORT_ORDER) or not lines[0].startswith(_STRAIGHT_HEADER):
+        raise ValueError("not a map/path_straight.txt")
+    result = {}
+    for key, line in zip(STRAIGHT_REPORT_ORDER, lines[2:]):
+        name, _, value = line.partition("\t")
+        if name != key:
+            raise ValueError(f"path_straight.txt: expected {key}, found {name}")
+        if key == "reachable":
+            if value not in ("True", "False"):
+                raise ValueError(f"path_straight.txt: reachable is {value!r}")
+            result[key] = value == "True"
+        else:
+            result[key] = int(value) if key in ("n_points", "n_lattice_points") else float(value)
+    rows = [[float(v) for v in line.split(" ")] for line in lines[2 + len(STRAIGHT_REPORT_ORDER):]]
+    if len(rows) != result["n_points"] or any(len(r) != 3 for r in rows):
+        raise ValueError("path_straight.txt: the waypoints do not match n_points")
+    return result, np.array(rows, dtype=np.float64).reshape(-1, 3)
+
+
+def straighten_config(value, what="tsdf.esdf.plan.straighten"):
+    """None when the config value (absent, a bool, or {enable, window}) switches straightening off, else the window;
+    ValueError for anything else."""
+    if value is None or value is False:
+        return None
+    if value is True:
+        return DEFAULT_WINDOW
+    if not isinstance(value, dict) or set(value) - {"enable", "window"} or not isinstance(value.get("enable", True), bool):
+        raise ValueError(f"{what} must be a bool or {{enable, window}} (got {value!r})")
+    window = _window(value.get("window", DEFAULT_WINDOW), what)
+    return window if value.get("enable", True) else None
 
 
 PATH_REPORT_ORDER = ("reachable", "length_m", "min_clearance_m", "n_points")

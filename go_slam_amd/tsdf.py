@@ -541,7 +541,59 @@ class ESDF:
         return lo[None, :] + cells.double() * self.voxel, self.dist[idx[:, 0], idx[:, 1], idx[:, 2]].min()
 
     @torch.no_grad()
-    def plan(self, start, goal, robot_radius=0.0, allow_unknown=False, snap=0.0, max_cost_m=None):
+    def _waypoints(self, route, passable, straighten, window):
+        """`route` as it is without `straighten`, else with the keys of `plan.with_waypoints` over `passable`."""
+        if not straighten:
+            return route
+        lo = torch.tensor(self.lo, dtype=torch.float64, device=self.device)[None, :]
+        return _plan.with_waypoints(route, passable, window, lambda c: lo + c.double() * self.voxel, self.voxel, self.d2,
+                                    self.dist, "ESDF.straighten")
+
+    @torch.no_grad()
+    def straighten(self, route, robot_radius=0.0, allow_unknown=False, window=_plan.DEFAULT_WINDOW):
+        """The dict `route` of `plan`, `explore` or `next_view` (not changed) with its straightened form added: the
+        shortest route over the path's own cells whose straight legs a robot of `robot_radius` may take
+        (plan.straighten over `passable(robot_radius, allow_unknown)`: give the radius the route was planned with, each
+        cell is tested against the `window` cells before it).  New keys: "waypoint_index" int32 [K], the kept cells'
+        positions in "cells", first and last always among them, "waypoints" int32 [K,3], "waypoint_points" float64 [K,3]
+        world coordinates, "straight_length_m" <= length_m, and "straight_min_clearance_m": `dist` at the cell with the
+        smallest d2 that the straight legs cross (gs_segment_min), so it rounds as min_clearance_m does.  An unreachable
+        route gets empty waypoints, inf and nan.  ValueError before the device is touched; RuntimeError when the route
+        does not pass over `passable` (another radius than it was planned with)."""
+        what = "ESDF.straighten"
+        self._radius_d2(robot_radius, what)
+        _plan._window(window, what)
+        if not isinstance(route, dict) or "cells" not in route:
+            raise ValueError(f"{what}: route is the dict of ESDF.plan, explore or next_view")
+        return self._waypoints(route, self.passable(robot_radius, allow_unknown), True, window)
+
+    @torch.no_grad()
+    def sees(self, a_world, b_world, robot_radius=0.0, allow_unknown=False):
+        """bool [n] on the device: whether a robot of `robot_radius` may go straight from the world point a_world[i] to
+        b_world[i] ([n,3], or one point each: then one bool [1]) -- plan.line_of_sight between the points' nearest
+        lattice points over `passable(robot_radius, allow_unknown)`.  A point outside the lattice sees nothing.
+        ValueError for points that are no finite [n,3] or a radius beyond the band, before the device is touched."""
+        what = "ESDF.sees"
+        self._radius_d2(robot_radius, what)
+        ends = []
+        for name, p in (("a_world", a_world), ("b_world", b_world)):
+            p = p.detach().cpu().numpy() if isinstance(p, torch.Tensor) else p
+            try:
+                p = np.asarray(p, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise ValueError(f"{what}: {name} must be world points [n,3] (got {p!r})") from None
+            p = p.reshape(1, 3) if p.shape == (3,) else p
+            if p.ndim != 2 or p.shape[1] != 3 or not np.isfinite(p).all():
+                raise ValueError(f"{what}: {name} must be finite world points [n,3] (got shape {list(p.shape)})")
+            cell = np.floor((p - self.lo[None, :]) / self.voxel + 0.5)
+            ends.append(np.clip(cell, -1, MAX_POINTS).astype(np.int32))      # outside stays outside
+        if ends[0].shape != ends[1].shape:
+            raise ValueError(f"{what}: a_world is {list(ends[0].shape)} and b_world is {list(ends[1].shape)}")
+        return _plan.line_of_sight(self.passable(robot_radius, allow_unknown), ends[0], ends[1])
+
+    @torch.no_grad()
+    def plan(self, start, goal, robot_radius=0.0, allow_unknown=False, snap=0.0, max_cost_m=None, straighten=False,
+             window=_plan.DEFAULT_WINDOW):
         """The shortest collision-free route of a robot of `robot_radius` from the world point `start` to `goal` over
         the lattice (plan.geodesic_field seeded at the goal, GeodesicField.path from the start).  A point maps to its
         nearest lattice point; with `snap` > 0 metres an endpoint whose cell does not pass moves to the passable cell
@@ -550,23 +602,27 @@ class ESDF:
         "cells": int32 [L,3] on the device, "points": float64 [L,3] world coordinates start to goal, "length_m":
         cost[start] * voxel / 1000, "min_clearance_m": the smallest `dist` over the path's cells, "start_cell",
         "goal_cell" (None when no passable cell was found), "sweeps"}; unreachable: L = 0, length_m inf,
-        min_clearance_m nan.  ValueError (plan_arguments) before the device is touched."""
+        min_clearance_m nan.  With `straighten` the dict gains the keys of `ESDF.straighten` (waypoint_index, waypoints,
+        waypoint_points, straight_length_m, straight_min_clearance_m; window as there); without it nothing else is
+        launched and the dict is the one above.  ValueError (plan_arguments; a bad window) before the device is
+        touched."""
         (s, g), snap_cells, max_cost = self.plan_arguments([start, goal], robot_radius, snap, max_cost_m)
+        _plan._window(window, "ESDF.plan")
         passable = self.passable(robot_radius, allow_unknown)
         s, g = _plan.snap_cell(passable, s, snap_cells), _plan.snap_cell(passable, g, snap_cells)
         out = self._no_route(s, g, 0)
         if s is None or g is None:
-            return out
+            return self._waypoints(out, passable, straighten, window)
         field = _plan.geodesic_field(passable, [g], max_cost)
         cells = field.path(s)
         out["sweeps"] = field.sweeps
         if int(cells.shape[0]) == 0:
-            return out
+            return self._waypoints(out, passable, straighten, window)
         points, clearance = self._route(cells)
         scalars = torch.stack([field.cost[s[0], s[1], s[2]].double(), clearance.double()]).cpu().tolist()   # one read
         out.update(reachable=True, cells=cells, points=points, length_m=scalars[0] * self.voxel / 1000.0,
                    min_clearance_m=scalars[1])
-        return out
+        return self._waypoints(out, passable, straighten, window)
 
     @torch.no_grad()
     def reachable(self, seeds_world, robot_radius=0.0, allow_unknown=False, snap=0.0, max_cost_m=None):
@@ -613,17 +669,24 @@ class ESDF:
         return out
 
     @torch.no_grad()
-    def explore(self, start, robot_radius=0.0, snap=0.0, max_cost_m=None, min_cells=1, order="nearest"):
+    def explore(self, start, robot_radius=0.0, snap=0.0, max_cost_m=None, min_cells=1, order="nearest", straighten=False,
+                window=_plan.DEFAULT_WINDOW):
         """Where to go next from the world point `start` to see something new: `frontiers(...)`, then among the kept
         clusters a route leads to, `order` "nearest" takes the smallest best_cost, ties to the lowest root, "largest" the
         largest faces, then the smallest best_cost, then the lowest root; the route is the field's path from the
         cluster's best_cell, reversed so that it reads start to goal.  -> `plan`'s dict {"reachable", "cells", "points",
         "length_m", "min_clearance_m", "start_cell", "goal_cell", "sweeps" (the field's)} plus "cluster" (the id or
         None), "n_clusters", "n_kept", "n_reachable" and "clusters" (the FrontierClusters of `frontiers`); when no
-        cluster qualifies, `plan`'s unreachable shape.  One read of the table's columns besides those of `frontiers`
-        and `plan`."""
+        cluster qualifies, `plan`'s unreachable shape.  `straighten` and `window` as for `plan`.  One read of the table's
+        columns besides those of `frontiers` and `plan`."""
         if order not in _frontier.ORDERS:
             raise ValueError(f"ESDF.explore: order must be one of {_frontier.ORDERS} (got {order!r})")
+        _plan._window(window, "ESDF.explore")
+        out = self._explore(start, robot_radius, snap, max_cost_m, min_cells, order)
+        return self._waypoints(out, self.passable(robot_radius), True, window) if straighten else out
+
+    def _explore(self, start, robot_radius, snap, max_cost_m, min_cells, order):
+        """`explore`'s route."""
         self.plan_arguments([start], robot_radius, snap, max_cost_m, "ESDF.explore")      # a start is needed here
         fc = self.frontiers(robot_radius, start, snap, max_cost_m, min_cells)
         out = dict(self._no_route(fc.start_cell, None, 0 if fc.field is None else fc.field.sweeps), cluster=None,
@@ -715,7 +778,8 @@ class ESDF:
                                           max_candidates)
 
     def next_view(self, start, camera, up_axis, height, n_yaw=8, robot_radius=0.0, stride=4, snap=0.0, max_cost_m=None,
-                  max_candidates=4096, max_unknown=0, min_gain_cells=1, min_solid_cells=0, lam=0.0):
+                  max_candidates=4096, max_unknown=0, min_gain_cells=1, min_solid_cells=0, lam=0.0, straighten=False,
+                  window=_plan.DEFAULT_WINDOW):
         """Where to stand, which way to look and how much of the unknown would be seen from there: the `view_candidates`,
         each looked from at the `n_yaw` headings 2 pi j / n_yaw about `up_axis` with `camera` = {hfov_deg, vfov_deg, n_u,
         n_v, range_m, pitch_deg} (view.ray_directions; range_m / voxel rounded down to cells) -- one gs_view_gain call per
@@ -725,9 +789,11 @@ class ESDF:
         lower cost, then the lower linear index, then the lower heading.  -> `plan`'s dict, the route start to view, plus
         "view_cell", "view_point", "yaw", "yaw_index", "gain_cells", "gain_m3", "free_cells", "solid_cells", "score",
         "n_candidates", "n_qualified" and "gains" (the device table); when nothing qualifies, `plan`'s unreachable shape
-        with "view_cell" None.  ValueError before the device is touched."""
-        return _view.esdf_next_view(self, start, camera, up_axis, height, n_yaw, robot_radius, stride, snap, max_cost_m,
-                                    max_candidates, max_unknown, min_gain_cells, min_solid_cells, lam)
+        with "view_cell" None.  `straighten` and `window` as for `plan`.  ValueError before the device is touched."""
+        _plan._window(window, "ESDF.next_view")
+        out = _view.esdf_next_view(self, start, camera, up_axis, height, n_yaw, robot_radius, stride, snap, max_cost_m,
+                                   max_candidates, max_unknown, min_gain_cells, min_solid_cells, lam)
+        return self._waypoints(out, self.passable(robot_radius), True, window) if straighten else out
 
     def save_map(self, directory, up_axis, height, robot_radius=0.0, known_fraction=0.5):
         """`occupancy_slice` written as `directory`/occupancy.pgm and occupancy.yaml (save_map); returns the slice."""
@@ -1016,7 +1082,10 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
     (ESDF.save_map), and with plan = {enable, robot_radius, allow_unknown, snap, start, goal} (absent by default; start
     and goal are world points or "last" / "first", the run's last and first camera centre, by default "last" and "first":
     the way home) the route of ESDF.plan into {output}/map/path.txt (plan.path_text; `tsdf_path_reachable` and
-    `tsdf_path_length_m` in `stats`), and with frontiers = {enable, robot_radius, min_cells, start, snap, order} (absent by
+    `tsdf_path_length_m` in `stats`) and, with plan.straighten (a bool or {enable, window}; absent by default; another
+    value is refused before anything is fused), the route's waypoints by straight legs into {output}/map/path_straight.txt
+    beside it (plan.straight_path_text; `tsdf_path_straight_length_m` and `tsdf_path_waypoints` in `stats`), and with
+    frontiers = {enable, robot_radius, min_cells, start, snap, order} (absent by
     default; start is a world point or "last", the default) the frontier clusters of ESDF.frontiers into
     {output}/map/frontiers.txt (frontier.frontiers_text) and, when ESDF.explore finds a goal, its route into
     {output}/map/explore_path.txt (plan.path_text; `tsdf_frontier_cells`, `tsdf_frontier_clusters`,
@@ -1111,6 +1180,9 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
     rm = (ed.get("rooms") or {}) if ed.get("enable", False) else {}
     if rm.get("enable", False):                             # refused before anything is fused or written
         rm_args = _rooms.config_arguments(rm, float(opt.get("voxel_size", 0.05)), ed.get("max_distance"))
+    pl_window = None
+    if ed.get("enable", False) and (ed.get("plan") or {}).get("enable", False):          # refused before anything is fused
+        pl_window = _plan.straighten_config(ed["plan"].get("straighten"), "fuse_from_config: tsdf.esdf.plan.straighten")
     bound =opt.get("bound") or slam.cfg["mapping"]["bound"]
     min_weight = float(opt.get("min_weight", 1.0))
     vol, mesh = fuse_keyframes(slam.video, bound, float(opt.get("voxel_size", 0.05)), source=opt.get("source", "tracked"),
@@ -1206,12 +1278,21 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
                     end = torch.as_tensor(nav_c2w[-1 if end == "last" else 0])[:3, 3]
                 ends.append(end)
             res = field.plan(ends[0], ends[1], robot_radius=pl.get("robot_radius", 0.0),
-                             allow_unknown=pl.get("allow_unknown", False), snap=pl.get("snap", 0.0))
+                             allow_unknown=pl.get("allow_unknown", False), snap=pl.get("snap", 0.0),
+                             **({} if pl_window is None else {"straighten": True, "window": pl_window}))
             os.makedirs(f"{slam.output}/map", exist_ok=True)
             with open(f"{slam.output}/map/path.txt", "w") as fh:
                 fh.write(_plan.path_text(res))
             if stats is not None:
                 stats.update(tsdf_path_reachable=res["reachable"], tsdf_path_length_m=res["length_m"])
+            if pl_window is not None:
+                with open(f"{slam.output}/map/path_straight.txt", "w") as fh:
+                    fh.write(_plan.straight_path_text(res))
+                if stats is not None:
+                    stats.update(tsdf_path_straight_length_m=res["straight_length_m"],
+                                 tsdf_path_waypoints=int(res["waypoints"].shape[0]))
+                print(f"TSDF straightened path: length_m {res['straight_length_m']!r}, min_clearance_m "
+                      f"{res['straight_min_clearance_m']!r}, {int(res['waypoints'].shape[0])} waypoints")
             print(f"TSDF path: reachable {res['reachable']!r}, length_m {res['length_m']!r}, "
                   f"min_clearance_m {res['min_clearance_m']!r}, {int(res['cells'].shape[0])} points")
             planned = res

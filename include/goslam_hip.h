@@ -822,6 +822,53 @@ int gs_room_door_table(const unsigned char* open, const int* label, const int* d
                        int n2, const int* root, int rows, int* size, long long* sum, int* bbox, int* room_lo, int* room_hi,
                        unsigned long long* widest, gs_stream_t stream);
 
+/* ---- Line of sight over a passability lattice and the shortest shortcut of a path (no counterpart in the reference),
+ *      csrc/sight_walk.h and csrc/sight.hip; tests/sight_restatement.py restates it serially ----
+ *
+ * The lattice, its linear index and passable u8 are those of the geodesic block above (each size in [1, 1024]).  A cell is
+ * three i32 (c0, c1, c2); a segment is six, a then b.  Everything is integer apart from one fp64 sqrt per leg length.
+ *
+ * Supercover of the cells a and b: the cells whose closed unit cube, centred on the lattice point, meets the closed
+ *   segment between the two centres.  a sees b over passable when both lie inside the lattice and every cell of the
+ *   supercover is passable.  The walk that lists it (sight_walk.h), d = b - a, w_k = |d_k|, g_k = sign(d_k), one counter
+ *   k_k per axis from 0 and the offset f from a, f = 0 at first:
+ *     a is visited first.  While some k_k < w_k: the axes with k_k < w_k cross next at (2 k_k + 1) / (2 w_k), compared
+ *     exactly by cross-multiplying (products below 2^21); S is the set of axes that hold the smallest crossing; the cells
+ *     a + f + sum_{k in T} g_k e_k are visited for every non-empty T within S (1, 3 or 7 cells: a segment through an edge
+ *     or a corner touches every cube around it, and a robot does not slip between two cells that touch there); then f
+ *     and k advance along every axis of S.  At most w_0 + w_1 + w_2 steps, no cell twice, every cell inside the box the
+ *     two ends span, the same set from b to a.  For a and b one move apart it is the box of the geodesic block's move
+ *     rule.
+ * len(a, b) = floor(sqrt(1000000 * |b - a|^2)), the leg's length in milli-voxels, in 64-bit integers (an fp64 sqrt and a
+ *   correction by one): 1000, 1414, 1732 for the 26 moves, at most 1771887.
+ *
+ * gs_segment_sight: segs i32 [n,6], n >= 0 (n == 0 launches nothing); out u8 [n], every element written: 1 when a sees
+ *   b, else 0 (an end outside the lattice: 0).
+ * gs_segment_min: field i32 [n0,n1,n2]; out_value i32 [n] the smallest field value over the supercover, out_cell i32
+ *   [n] the lowest linear index that holds it; an end outside the lattice: INT32_MIN and -1.
+ * gs_path_sight: cells i32 [L,3], 1 <= L <= GS_PATH_MAX_CELLS; window W with 1 <= W <= L - 1, or W == 1 when L == 1;
+ *   sight u64 [L, ceil(W / 64)], 8-byte aligned, every word written: bit (b & 63) of word b / 64 of row j is set iff
+ *   0 <= b < min(W, j) and cell j - 1 - b sees cell j; every other bit is 0.  A path cell outside the lattice or not
+ *   passable sees nothing and is seen by nothing.
+ * gs_path_shortcut: sight and cells as gs_path_sight wrote and read them, the same L and W.  The shortest route from
+ *   cell 0 to cell L - 1 over the path's own cells whose legs see: dp[0] = 0, dp[j] = the minimum over the i with bit
+ *   j - 1 - i of row j set and dp[i] reached of dp[i] + len(i, j), ties to the lowest i; a sum of 2^31 - 1 or more
+ *   counts as not reached (a path of adjacent cells stays below 2^25).  n_out i32 [1] = K, the number of cells kept,
+ *   index i32 [L] of which [0, K) are written, ascending, index[0] = 0 and index[K - 1] = L - 1, and length i32 [1] =
+ *   dp[L - 1].  When cell L - 1 is not reached n_out = -1 and nothing else is written.  One workgroup; dp and the
+ *   predecessors take 6 L bytes of LDS.
+ * A NULL pointer, a size outside [1, 1024], n < 0, L or W outside the ranges above or a misaligned sight return
+ * GS_ERR_INVALID_ARG before anything is launched or written; every entry enqueues on the stream and reads nothing back. */
+#define GS_PATH_MAX_CELLS 16384
+int gs_segment_sight(const unsigned char* passable, int n0, int n1, int n2, const int* segs, int n, unsigned char* out,
+                     gs_stream_t stream);
+int gs_segment_min(const int* field, int n0, int n1, int n2, const int* segs, int n, int* out_value, int* out_cell,
+                   gs_stream_t stream);
+int gs_path_sight(const unsigned char* passable, int n0, int n1, int n2, const int* cells, int L, int window,
+                  unsigned long long* sight, gs_stream_t stream);
+int gs_path_shortcut(const unsigned long long* sight, const int* cells, int L, int window, int* index, int* n_out,
+                     int* length, gs_stream_t stream);
+
 /* ---- View gain: the cells of a state lattice that a camera's rays cross from a candidate pose (no counterpart in the
  *      reference), csrc/view_gain.hip; tests/view_gain_restatement.py restates it serially ----
  *
