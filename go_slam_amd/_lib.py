@@ -105,7 +105,11 @@ SIGNATURES = {
     "gs_segment_min": (c_int, [_P] + [c_int] * 3 + [_P, c_int, _P, _P, _P]),
     "gs_path_sight": (c_int, [_P] + [c_int] * 3 + [_P, c_int, c_int, _P, _P]),
     "gs_path_shortcut": (c_int, [_P, _P, c_int, c_int, _P, _P, _P, _P]),
-    "gs_view_gain_lds_bytes": (c_size_t, [ctypes.POINTER(c_int)]),
+    "gs_follow_rollouts": (c_int, [_P, _P] + [c_int] * 3 + [c_float] * 4 + [c_int] + [c_float] * 5 + [_P, _P] + [c_int] * 2
+                           + [c_float] * 10 + [_P] * 4 + [_P]),
+    "gs_follow_weights": (c_int, [_P, c_int, c_float] + [_P] * 4 + [_P]),
+    "gs_follow_update": (c_int, [_P] * 4 + [c_int] * 2 + [c_float] * 2 + [c_int] + [_P] * 2 + [_P]),
+    "gs_view_gain_lds_bytes":(c_size_t, [ctypes.POINTER(c_int)]),
     "gs_view_gain": (c_int, [_P] + [c_int] * 3 + [_P, c_int, _P] + [c_int] * 3 + [ctypes.POINTER(c_int), _P, _P]),
     "gs_frame_prep_color": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P]),
     "gs_frame_prep_depth": (c_int, [_P, c_int, c_float, c_int, c_int, c_int, c_int, _P]),

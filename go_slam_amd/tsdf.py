@@ -58,6 +58,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import follow as _follow
 from . import frontier as _frontier
 from . import localize as _localize
 from . import plan as _plan
@@ -625,6 +626,43 @@ class ESDF:
         return self._waypoints(out, passable, straighten, window)
 
     @torch.no_grad()
+    def follow(self, start, goal, up_axis, heading=None, max_ticks=400, goal_tolerance=_follow.DEFAULT_TOLERANCE,
+               **controller_args):
+        """Drive a differential-drive base from the world point `start` to `goal` in the plane perpendicular to
+        `up_axis` at `start`'s coordinate on it: `follow.Controller(self, goal, up_axis, height, **controller_args)` and
+        its `drive` from `start` heading along `heading`, a direction (c, s) on the plane's two axes in increasing order
+        (normalised here; default: down the cost-to-go field's first path step, (1, 0) where that step leaves the plane
+        or there is none).  -> `Controller.drive`'s dict with "goal_cell" and "start_cell" added.  An unreachable goal
+        gives reached False and empty traces with nothing launched beyond the field.  ValueError before the device is
+        touched."""
+        what = "ESDF.follow"
+        robot_radius = controller_args.get("robot_radius", 0.0)
+        (s_cell,), _, _ = self.plan_arguments([start], robot_radius, 0.0, None, what)
+        if isinstance(up_axis, bool) or not isinstance(up_axis, (int, np.integer)) or not 0 <= int(up_axis) <= 2:
+            raise ValueError(f"{what}: up_axis must be 0, 1 or 2 (got {up_axis!r})")
+        if heading is not None:
+            try:
+                heading = [float(v) for v in heading]
+            except (TypeError, ValueError):
+                heading = []
+            if len(heading) != 2 or not all(math.isfinite(v) for v in heading) or math.hypot(*heading) == 0:
+                raise ValueError(f"{what}: heading is a direction (c, s) in the plane of motion (got {heading!r})")
+        start = [float(v) for v in (start.tolist() if hasattr(start, "tolist") else start)]
+        u, v = [ax for ax in range(3) if ax != int(up_axis)]
+        controller_args.setdefault("robot_radius", robot_radius)
+        ctl = _follow.Controller(self, goal, int(up_axis), start[int(up_axis)], **controller_args)
+        if heading is None:
+            heading = [1.0, 0.0]
+            if ctl.goal_cell is not None:
+                cells = ctl.field.path(s_cell, max_len=None)[:2].cpu().tolist()
+                if len(cells) == 2 and (cells[1][u] != cells[0][u] or cells[1][v] != cells[0][v]):
+                    heading = [float(cells[1][u] - cells[0][u]), float(cells[1][v] - cells[0][v])]
+        norm = math.hypot(*heading)
+        out = ctl.drive([start[u], start[v], heading[0] / norm, heading[1] / norm], max_ticks, goal_tolerance)
+        out.update(goal_cell=ctl.goal_cell, start_cell=s_cell)
+        return out
+
+    @torch.no_grad()
     def reachable(self, seeds_world, robot_radius=0.0, allow_unknown=False, snap=0.0, max_cost_m=None):
         """bool [nx,ny,nz]: the cells a robot of `robot_radius` can reach from any of the world points `seeds_world`
         ([m,3], for example every camera centre), i.e. cost < INF of the field seeded at all of them.  Seeds are placed
@@ -1084,7 +1122,11 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
     the way home) the route of ESDF.plan into {output}/map/path.txt (plan.path_text; `tsdf_path_reachable` and
     `tsdf_path_length_m` in `stats`) and, with plan.straighten (a bool or {enable, window}; absent by default; another
     value is refused before anything is fused), the route's waypoints by straight legs into {output}/map/path_straight.txt
-    beside it (plan.straight_path_text; `tsdf_path_straight_length_m` and `tsdf_path_waypoints` in `stats`), and with
+    beside it (plan.straight_path_text; `tsdf_path_straight_length_m` and `tsdf_path_waypoints` in `stats`), and, with
+    plan.follow = {enable, up_axis, heading, max_ticks, goal_tolerance and follow.Controller's keys; absent by default;
+    robot_radius and allow_unknown default to the plan's; a bad value is refused before anything is fused}, the closed-loop
+    drive of ESDF.follow between the route's two end cells into {output}/map/follow.txt (follow.follow_text;
+    `tsdf_follow_reached`, `tsdf_follow_ticks` and `tsdf_follow_min_clearance_m` in `stats`), and with
     frontiers = {enable, robot_radius, min_cells, start, snap, order} (absent by
     default; start is a world point or "last", the default) the frontier clusters of ESDF.frontiers into
     {output}/map/frontiers.txt (frontier.frontiers_text) and, when ESDF.explore finds a goal, its route into
@@ -1180,9 +1222,10 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
     rm = (ed.get("rooms") or {}) if ed.get("enable", False) else {}
     if rm.get("enable", False):                             # refused before anything is fused or written
         rm_args = _rooms.config_arguments(rm, float(opt.get("voxel_size", 0.05)), ed.get("max_distance"))
-    pl_window = None
+    pl_window = pl_follow = None
     if ed.get("enable", False) and (ed.get("plan") or {}).get("enable", False):          # refused before anything is fused
         pl_window = _plan.straighten_config(ed["plan"].get("straighten"), "fuse_from_config: tsdf.esdf.plan.straighten")
+        pl_follow = _follow.follow_config(ed["plan"].get("follow"), "fuse_from_config: tsdf.esdf.plan.follow")
     bound =opt.get("bound") or slam.cfg["mapping"]["bound"]
     min_weight = float(opt.get("min_weight", 1.0))
     vol, mesh = fuse_keyframes(slam.video, bound, float(opt.get("voxel_size", 0.05)), source=opt.get("source", "tracked"),
@@ -1296,6 +1339,24 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
             print(f"TSDF path: reachable {res['reachable']!r}, length_m {res['length_m']!r}, "
                   f"min_clearance_m {res['min_clearance_m']!r}, {int(res['cells'].shape[0])} points")
             planned = res
+            if pl_follow is not None:
+                drove = _follow.no_drive()
+                if res["start_cell"] is not None and res["goal_cell"] is not None:
+                    # between the cells the route was planned between: camera centres usually sit in cells that do not pass
+                    lo = torch.tensor(field.lo, dtype=torch.float64)
+                    drive_args = dict(pl_follow[1])
+                    drive_args.setdefault("robot_radius", pl.get("robot_radius", 0.0))
+                    drive_args.setdefault("allow_unknown", pl.get("allow_unknown", False))
+                    drove = field.follow(lo + torch.tensor(res["start_cell"], dtype=torch.float64) * field.voxel,
+                                         lo + torch.tensor(res["goal_cell"], dtype=torch.float64) * field.voxel,
+                                         pl_follow[0], **drive_args)
+                with open(f"{slam.output}/map/follow.txt", "w") as fh:
+                    fh.write(_follow.follow_text(drove))
+                if stats is not None:
+                    stats.update(tsdf_follow_reached=drove["reached"], tsdf_follow_ticks=drove["ticks"],
+                                 tsdf_follow_min_clearance_m=drove["min_clearance_m"])
+                print(f"TSDF follow: reached {drove['reached']!r}, ticks {drove['ticks']!r}, length_m "
+                      f"{drove['length_m']!r}, min_clearance_m {drove['min_clearance_m']!r}, stops {drove['stops']!r}")
         fr = ed.get("frontiers") or {}
         if fr.get("enable", False):
             start = nav_point(fr.get("start", "last"))

@@ -869,6 +869,63 @@ int gs_path_sight(const unsigned char* passable, int n0, int n1, int n2, const i
 int gs_path_shortcut(const unsigned long long* sight, const int* cells, int L, int window, int* index, int* n_out,
                      int* length, gs_stream_t stream);
 
+/* ---- Following a route: a sampled-rollout (model-predictive path-integral) controller of a differential-drive base over
+ *      the distance field and a cost-to-go field (no counterpart in the reference), csrc/follow.hip;
+ *      tests/follow_restatement.py restates it serially ----
+ *
+ * The lattice is gs_esdf_query's (n0 x n1 x n2, the last axis contiguous, each size in [2, 1024], lo, voxel).  dist f32
+ * [n0,n1,n2] is gs_esdf_build's; togo i32 [n0,n1,n2] is a gs_geodesic_* cost field seeded at the goal, in milli-voxels,
+ * >= INF = 0x3fffffff where the robot's centre may not be.  The robot moves in the plane perpendicular to up_axis in
+ * {0, 1, 2} at the world coordinate `height` on it; the two other axes, in increasing order, are (u, v), as in
+ * gs_esdf_slice.  State (x, y, c, s): the position on (u, v) in metres and the heading as a unit vector.  Controls (v, w):
+ * speed in m/s and yaw rate in rad/s, 0 <= v <= v_max, |w| <= w_max.  K rollouts, 1 <= K <= GS_FOLLOW_MAX_ROLLOUTS, of
+ * T steps, 1 <= T <= GS_FOLLOW_MAX_STEPS; U f32 [T,2] the nominal controls, noise f32 [T,K,2], both 8-byte aligned.
+ *
+ * Everything of a rollout is fp32, one rounding per operation, no fma, in exactly this order.
+ *   control(U[t], noise[t,k]): per component a = U + noise, a = U when a is NaN or +-inf; then
+ *     v = a_v < 0 ? 0 : (a_v > v_max ? v_max : a_v) ; w = a_w < -w_max ? -w_max : (a_w > w_max ? w_max : a_w)
+ *   step: h = (0.5 * dt) * w ; den = 1 + h * h ; cr = (1 - h * h) / den ; sr = (2 * h) / den
+ *         c' = c * cr - s * sr ; s' = s * cr + c * sr ; x' = x + (dt * v) * c' ; y' = y + (dt * v) * s'
+ *     (Cayley's form of a rotation: exactly one by 2 atan(h), which is w dt up to (w dt)^3 / 12, and no transcendental.)
+ *   sample(x, y): the world point p with p[up_axis] = height, p[u] = x, p[v] = y; per axis g = (p - lo) / voxel and
+ *     a = floorf(g).  It is a collision when not 0 <= a < float(n - 1) on every axis (compared as floats; NaN fails) or
+ *     when togo at the nearest lattice point (int)floorf(g + 0.5) is >= INF.  Otherwise
+ *       d = gs_esdf_query's out_dist, the lerps z, then y, then x of the cell's corners of dist at g - a
+ *       togo_term = w_togo * (float(togo) * (voxel / 1000)) ; cost = togo_term
+ *       cost = cost + (w_clear * ((robot_radius + margin) - d)) / margin        only when d < robot_radius + margin
+ *   rollout k: state = the start; frozen = sample(start).cost and last = its togo_term, both 0 when the start collides;
+ *     S = 0 ; hit = T ; closest = +inf.  For t = 0 .. T - 1, while hit == T: the control, the step, the sample of the
+ *     stepped point.  Live: the state moves there, frozen = cost + w_turn * (w * w), last = togo_term, closest = d where
+ *     d < closest, S = S + frozen.  A collision: hit = t, S = S + collision_cost, then S = S + frozen, and the state
+ *     stays.  Every later step: S = S + frozen.  After the loop S = S + w_end * last when hit == T.
+ * gs_follow_rollouts: outputs S f32 [K], end f32 [K,4] the last state, hit_step i32 [K] (T: never collided), min_dist f32
+ *   [K] (closest), every element written.  One lane per rollout.
+ * gs_follow_weights: S f32 [K] without NaN -> s_min f32 [1] the smallest S, best i32 [1] the lowest k that holds it,
+ *   omega f64 [K] = exp(-(double(S[k]) - double(s_min)) / double(lambda)), stats f64 [2] = (eta, ess) with eta = sum omega
+ *   and ess = eta * eta / sum omega^2.  One workgroup.
+ * gs_follow_update: per step t, delta[t,k] = control(U[t], noise[t,k]) - U[t] per component in fp32, the perturbation the
+ *   rollout applied (recomputed, nothing [T,K,2] is stored), mean = sum_k omega[k] * double(delta[t,k]) / stats[0] in
+ *   fp64, row = U[t] + float(mean) clamped as the control is.  shift == 0: U_new[t] = row.  shift == 1: U_new[t - 1] = row
+ *   for t >= 1 and U_new[T - 1] = row of T - 1 as well (the last row is repeated).  u_exec f32 [2] gets row 0 (needed with
+ *   shift == 1; may be NULL without).  U_new f32 [T,2] is another buffer than U.  One workgroup per step.
+ * Sums over k: a thread adds the elements k = tid, tid + threads, ... in that order, a wave adds by the xor butterfly
+ *   (offsets 32 .. 1), thread 0 adds the waves' sums in increasing order; no atomics, so the same inputs give the same
+ *   bits, and any order is within K * 2^-52 relative of the exact sum since every term of eta is positive.
+ * Bad sizes, a NULL or misaligned pointer, a parameter that is not finite, dt, v_max, w_max, margin, voxel or lambda that
+ * is not positive, a negative weight, radius or collision_cost return GS_ERR_INVALID_ARG before anything is launched or
+ * written; every entry enqueues on the stream and reads nothing back.                                                  */
+#define GS_FOLLOW_MAX_ROLLOUTS 65536
+#define GS_FOLLOW_MAX_STEPS 256
+int gs_follow_rollouts(const float* dist, const int* togo, int n0, int n1, int n2, float lo_x, float lo_y, float lo_z,
+                       float voxel, int up_axis, float height, float x, float y, float c, float s, const float* U,
+                       const float* noise, int K, int T, float dt, float v_max, float w_max, float robot_radius,
+                       float margin, float w_togo, float w_clear, float w_turn, float w_end, float collision_cost,
+                       float* S, float* end, int* hit_step, float* min_dist, gs_stream_t stream);
+int gs_follow_weights(const float* S, int K, float lambda, float* s_min, int* best, double* omega, double* stats,
+                      gs_stream_t stream);
+int gs_follow_update(const float* U, const float* noise, const double* omega, const double* stats, int K, int T,
+                     float v_max, float w_max, int shift, float* U_new, float* u_exec, gs_stream_t stream);
+
 /* ---- View gain: the cells of a state lattice that a camera's rays cross from a candidate pose (no counterpart in the
  *      reference), csrc/view_gain.hip; tests/view_gain_restatement.py restates it serially ----
  *
