@@ -109,6 +109,8 @@ SIGNATURES = {
                            + [c_float] * 10 + [_P] * 4 + [_P]),
     "gs_follow_weights": (c_int, [_P, c_int, c_float] + [_P] * 4 + [_P]),
     "gs_follow_update": (c_int, [_P] * 4 + [c_int] * 2 + [c_float] * 2 + [c_int] + [_P] * 2 + [_P]),
+    "gs_floor_columns": (c_int, [_P] + [c_int] * 8 + [_P, _P, _P]),
+    "gs_floor_footprint": (c_int, [_P, _P] + [c_int] * 4 + [_P, _P, _P, _P]),
     "gs_view_gain_lds_bytes":(c_size_t, [ctypes.POINTER(c_int)]),
     "gs_view_gain": (c_int, [_P] + [c_int] * 3 + [_P, c_int, _P] + [c_int] * 3 + [ctypes.POINTER(c_int), _P, _P]),
     "gs_frame_prep_color": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P]),

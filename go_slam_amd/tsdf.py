@@ -58,6 +58,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import floor as _floor
 from . import follow as _follow
 from . import frontier as _frontier
 from . import localize as _localize
@@ -477,6 +478,42 @@ class ESDF:
         _lib.check(rc, "ESDF.occupancy_slice")
         return {"cells": cells, "clearance": clearance, "resolution": self.voxel, "axes": (u, v),
                 "origin": (float(self.lo[u] - 0.5 * self.voxel), float(self.lo[v] - 0.5 * self.voxel))}
+
+    def floor_arguments(self, up_axis, height, robot_radius, robot_height, step_height, up_sign=+1):
+        """(up_axis, up_sign, p0, p1, H, S, R2) of gs_floor_columns and gs_floor_footprint for `floor_map`'s arguments, or
+        ValueError.  Touches no device."""
+        what = "ESDF.floor_map"
+        a, sign = _floor._axis_sign(up_axis, up_sign, what)
+        _, k0, k1, _, _ = self.slice_arguments(a, height)
+        H, S, R2 = _floor.robot_arguments(self.voxel, robot_radius, robot_height, step_height, what)
+        top = self.dims[a] - 1
+        p0, p1 = (k0, k1) if sign > 0 else (top - k1, top - k0)
+        return a, sign, p0, p1, H, S, R2
+
+    @torch.no_grad()
+    def floor_map(self, up_axis, height, robot_radius, robot_height, step_height, up_sign=+1):
+        """The map of where a ground robot can stand and roll (floor.columns, floor.footprint): a
+        disc of `robot_radius` metres, `robot_height` metres tall, that takes steps of `step_height` metres, on the floor
+        whose stand cells lie in the layers with height[0] <= lo + k * voxel <= height[1] along `up_axis` (`up_sign` -1:
+        up is the axis' negative direction).  A column is drivable (cells 254) when under the whole disc there is seen
+        support with free headroom and no height difference above the step; occupied (0) when the disc meets a column
+        without floor -- a wall, a table too low, a hole seen free to the bottom -- or a step too high; else unknown
+        (205): floor or headroom not observed yet.  -> `occupancy_slice`'s dict {"cells", "origin", "resolution", "axes"}
+        with "floor" int16 [n_u,n_v] (the lattice index of the stand cell, -1 without), "floor_height" float32 (the world
+        coordinate along up of its lower face, NaN without), "kind" uint8 (0 never observed, 1 floor, 2 maybe, 3 none),
+        "why" uint8 (of an occupied column: 1 no floor, 2 no floor under the disc, 3 a step), "rough" int16 (the largest
+        height difference under the disc in cells), "up_axis" and "up_sign"; images on the field's device.  H =
+        ceil(robot_height / voxel), S = floor(step_height / voxel), R2 = floor((robot_radius / voxel)^2).  Enqueues on
+        the current stream and reads nothing back.  ValueError for an empty range, a value that is not finite or
+        negative, or a radius below sqrt(2) or above 32 cells, before the device is touched."""
+        a, sign, p0, p1, H, S, R2 = self.floor_arguments(up_axis, height, robot_radius, robot_height, step_height, up_sign)
+        u, v = [ax for ax in range(3) if ax != a]
+        floor, kind = _floor.columns(self.state, a, sign, p0, p1, H)
+        cells, why, rough = _floor.footprint(floor, kind, R2, S)
+        return {"cells": cells, "resolution": self.voxel, "axes": (u, v),
+                "origin": (float(self.lo[u] - 0.5 * self.voxel), float(self.lo[v] - 0.5 * self.voxel)),
+                "floor": floor, "floor_height": _floor.floor_heights(floor, self.lo[a], self.voxel, sign), "kind": kind,
+                "why": why, "rough": rough, "up_axis": a, "up_sign": sign}
 
     def _radius_d2(self, robot_radius, what):
         """floor((robot_radius / voxel)^2), the squared lattice distance a passable cell must exceed; ValueError for a
@@ -1141,7 +1178,13 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
     the file lists the room of every object (in the map frame when upright), with plan on, the rooms and doorways along
     map/path.txt, and camera_room is the room of the last camera centre, moved by `snap` metres to a cell the robot may
     be at; values that are no numbers with 0 <= robot_radius < core_radius (within max_distance), min_core_m3 > 0 and
-    snap >= 0 are refused before anything is fused or written.  With
+    snap >= 0 are refused before anything is fused or written, and with floor = {enable, up_axis, up_sign, height,
+    robot_radius, robot_height, step_height, plan} (absent by default) the drivable-floor map of ESDF.floor_map into
+    {output}/map/floor/occupancy.pgm and occupancy.yaml (save_map) and its areas into {output}/map/floor.txt
+    (floor.floor_text; `tsdf_floor_map_drivable_m2` and `tsdf_floor_map_unknown_m2` in `stats`), and with floor.plan (needs
+    plan on) the route of plan_on_map on that map between the end cells of map/path.txt, put on the floor by floor.lift,
+    into {output}/map/floor_path.txt (plan.path_text; `tsdf_floor_path_reachable` and `tsdf_floor_path_length_m` in
+    `stats`); a bad value is refused before anything is fused or written.  With
     cfg["tsdf"]["save_volume"] the fused volume goes to {output}/mesh/tsdf_volume.npz (TSDFVolume.save), and with
     cfg["tsdf"]["align"] = {enable, every, levels, huber, max_depth, min_count} (absent by default; rgbd mode only) every
     `every`-th frame of `stream` is aligned to the fused volume from its pose in `c2w_list` (localize.align_stream, in
@@ -1226,6 +1269,11 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
     if ed.get("enable", False) and (ed.get("plan") or {}).get("enable", False):          # refused before anything is fused
         pl_window = _plan.straighten_config(ed["plan"].get("straighten"), "fuse_from_config: tsdf.esdf.plan.straighten")
         pl_follow = _follow.follow_config(ed["plan"].get("follow"), "fuse_from_config: tsdf.esdf.plan.follow")
+    fm = None
+    if ed.get("enable", False):                             # refused before anything is fused or written
+        fm = _floor.floor_config(ed.get("floor"), float(opt.get("voxel_size", 0.05)))
+        if fm is not None and fm["plan"] and not (ed.get("plan") or {}).get("enable", False):
+            raise ValueError("fuse_from_config: tsdf.esdf.floor.plan replans the route of tsdf.esdf.plan, which is off")
     bound =opt.get("bound") or slam.cfg["mapping"]["bound"]
     min_weight = float(opt.get("min_weight", 1.0))
     vol, mesh = fuse_keyframes(slam.video, bound, float(opt.get("voxel_size", 0.05)), source=opt.get("source", "tracked"),
@@ -1424,6 +1472,33 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
                 stats.update(tsdf_rooms_found=report["n_rooms"], tsdf_doors_found=report["n_doors"])
             print(f"TSDF rooms: {report['n_rooms']} rooms and {report['n_doors']} doorways over {report['n_open']} open "
                   f"cells, {report['n_core']} of them core, camera in room {report['camera_room']!r}")
+        if fm is not None:
+            grid = field.floor_map(fm["up_axis"], fm["height"], fm["robot_radius"], fm["robot_height"], fm["step_height"],
+                                   fm["up_sign"])
+            report = _floor.summary(grid)
+            save_map(f"{slam.output}/map/floor", grid)      # save_map's file names are fixed: a directory of its own
+            with open(f"{slam.output}/map/floor.txt", "w") as fh:
+                fh.write(_floor.floor_text(report))
+            if stats is not None:
+                stats.update(tsdf_floor_map_drivable_m2=report["drivable_m2"], tsdf_floor_map_unknown_m2=report["unknown_m2"])
+            print("TSDF floor map: " + ", ".join(f"{k} {report[k]!r}" for k in _floor.FLOOR_REPORT_ORDER))
+            if fm["plan"]:
+                route = {"reachable": False, "length_m": math.inf, "points": np.zeros((0, 3))}
+                if planned["start_cell"] is not None and planned["goal_cell"] is not None:
+                    # between the cells the 3-D route was planned between, as plan.follow does
+                    u, v = grid["axes"]
+                    ends = [(field.lo[u] + cell[u] * field.voxel, field.lo[v] + cell[v] * field.voxel)
+                            for cell in (planned["start_cell"], planned["goal_cell"])]
+                    res = _plan.plan_on_map(grid, ends[0], ends[1])
+                    if res["reachable"]:
+                        route = {"reachable": True, "length_m": res["length_m"], "points": _floor.lift(grid, res["cells"])}
+                route["min_clearance_m"] = math.nan         # the floor map has no clearance field
+                with open(f"{slam.output}/map/floor_path.txt", "w") as fh:
+                    fh.write(_plan.path_text(route))
+                if stats is not None:
+                    stats.update(tsdf_floor_path_reachable=route["reachable"], tsdf_floor_path_length_m=route["length_m"])
+                print(f"TSDF floor path: reachable {route['reachable']!r}, length_m {route['length_m']!r}, "
+                      f"{int(route['points'].shape[0])} points")
     if opt.get("save_volume", False):
         vol.save(f"{slam.output}/mesh/tsdf_volume.npz")
     if merged is not None:

@@ -926,6 +926,46 @@ int gs_follow_weights(const float* S, int K, float lambda, float* s_min, int* be
 int gs_follow_update(const float* U, const float* noise, const double* omega, const double* stats, int K, int T,
                      float v_max, float w_max, int shift, float* U_new, float* u_exec, gs_stream_t stream);
 
+/* ---- Drivable floor: an elevation map of a state lattice and the map of where a ground robot's base can stand and roll
+ *      on it (no counterpart in the reference), csrc/floor.hip; tests/floor_restatement.py restates it serially
+ *       ----
+ *
+ * state u8 [nx,ny,nz] is gs_esdf_build's (0 unseen, 1 free, 2 solid), each size in [2, 1024].  up_axis in {0, 1, 2},
+ * up_sign in {+1, -1}.  The position p along up of the lattice index k is k for up_sign = +1 and n_a - 1 - k for -1, n_a
+ * the size along up_axis; "above" is a larger p; a position beyond the lattice counts as unseen.  The two other axes, in
+ * increasing order, are (u, v) and index every image [n_u,n_v], as in gs_esdf_slice.  Integers only, no atomics: the same
+ * inputs give the same bits for every up_axis.
+ *
+ * gs_floor_columns: the band 0 <= p0 <= p1 < n_a of positions the robot's base may rest at, the headroom H >= 1 in cells.
+ *   Per column a position p is a stand when p >= 1, state[p - 1] == 2 (seen support directly beneath) and state[j] != 2
+ *   for every j in p .. p + H - 1; it is strict when all those cells lie inside the lattice and are free (== 1).  With F
+ *   the lowest stand in p0 <= p <= p1, floor i16 [n_u,n_v] and kind u8 [n_u,n_v], every element written:
+ *     F strict                      floor = the lattice index k of F (not p), kind = 1
+ *     F not strict ("maybe")        floor = the lattice index k of F,         kind = 2
+ *     no stand, no cell at a position in [max(p0 - 1, 0), min(p1 + H - 1, n_a - 1)] is solid and at least one of them is
+ *       unseen (the floor was never observed)                                 floor = -1, kind = 0
+ *     anything else (a wall, too low, a hole seen free to the bottom)         floor = -1, kind = 3
+ *   One walk per column over exactly those positions.
+ * gs_floor_footprint: floor, kind [n_u,n_v] as above, n_u and n_v in [2, 1024]; the robot's disc is the offsets (du, dv)
+ *   with du * du + dv * dv <= R2, 2 <= R2 <= 1024 (the eight neighbours always belong to it, so a move between two
+ *   drivable neighbours never climbs more than S); S >= 0 the largest height difference in cells inside the disc.  A
+ *   column q of the disc outside the map counts as kind 0.  Per column c, cells u8 (254 free, 0 occupied, 205 unknown: a
+ *   map_server PGM's values), why u8 and rough i16, all [n_u,n_v], every element written, rules in this order:
+ *     kind[c] == 3                                                      cells = 0,   why = 1
+ *     kind[c] == 0                                                      cells = 205, why = 0
+ *     some q of the disc has kind 3                                     cells = 0,   why = 2
+ *     some q of kind 1 or 2 has |floor[q] - floor[c]| > S               cells = 0,   why = 3
+ *     kind[c] == 2 or some q has kind 0 or 2                            cells = 205, why = 0
+ *     otherwise                                                         cells = 254, why = 0
+ *   rough[c] = the largest |floor[q] - floor[c]| over the disc's columns of kind 1 or 2; 0 when kind[c] is 0 or 3.
+ * A NULL pointer, a size outside [2, 1024], a bad axis or sign, an empty or out-of-range band, H < 1, S < 0 or R2 outside
+ * its range return GS_ERR_INVALID_ARG before anything is launched or written; both entries enqueue on the stream and read
+ * nothing back.                                                                                                        */
+int gs_floor_columns(const unsigned char* state, int nx, int ny, int nz, int up_axis, int up_sign, int p0, int p1, int H,
+                     short* floor, unsigned char* kind, gs_stream_t stream);
+int gs_floor_footprint(const short* floor, const unsigned char* kind, int n_u, int n_v, int R2, int S,
+                       unsigned char* cells, unsigned char* why, short* rough, gs_stream_t stream);
+
 /* ---- View gain: the cells of a state lattice that a camera's rays cross from a candidate pose (no counterpart in the
  *      reference), csrc/view_gain.hip; tests/view_gain_restatement.py restates it serially ----
  *
