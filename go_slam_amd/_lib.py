@@ -113,6 +113,9 @@ SIGNATURES = {
     "gs_floor_footprint": (c_int, [_P, _P] + [c_int] * 4 + [_P, _P, _P, _P]),
     "gs_view_gain_lds_bytes":(c_size_t, [ctypes.POINTER(c_int)]),
     "gs_view_gain": (c_int, [_P] + [c_int] * 3 + [_P, c_int, _P] + [c_int] * 3 + [ctypes.POINTER(c_int), _P, _P]),
+    "gs_scan_cast": (c_int, [_P, c_int, c_int, _P, c_int, _P] + [c_int] * 3 + [_P, _P, _P, _P]),
+    "gs_scan_field": (c_int, [_P, c_int, c_int, c_int, _P, _P]),
+    "gs_scan_match": (c_int, [_P, _P, c_int, c_int, _P] + [c_int] * 8 + [_P, _P, _P]),
     "gs_frame_prep_color": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P]),
     "gs_frame_prep_depth": (c_int, [_P, c_int, c_float, c_int, c_int, c_int, c_int, _P]),
     "gs_cvx_upsample":(c_int, [_P] * 4 + [c_int] * 4 + [_P]),

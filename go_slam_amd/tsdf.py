@@ -64,6 +64,7 @@ from . import frontier as _frontier
 from . import localize as _localize
 from . import plan as _plan
 from . import rooms as _rooms
+from . import scan as _scan
 from . import tsdf_merge as _merge
 from . import tsdf_objects as _objects
 from . import tsdf_planes as _planes
@@ -1184,7 +1185,12 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
     (floor.floor_text; `tsdf_floor_map_drivable_m2` and `tsdf_floor_map_unknown_m2` in `stats`), and with floor.plan (needs
     plan on) the route of plan_on_map on that map between the end cells of map/path.txt, put on the floor by floor.lift,
     into {output}/map/floor_path.txt (plan.path_text; `tsdf_floor_path_reachable` and `tsdf_floor_path_length_m` in
-    `stats`); a bad value is refused before anything is fused or written.  With
+    `stats`); a bad value is refused before anything is fused or written, and with scan = {up_axis, height, beams, fov_deg,
+    max_range, every, n_yaw, window_m} (absent by default; scan.scan_config) the occupancy slice at robot radius 0 of those
+    layers, on which a range scan is cast at every `every`-th pose of `c2w_list` whose cell is free (the camera centre on
+    the map's two axes, the yaw of the optical axis projected onto them) and found again by scan.localize_on_map within
+    window_m metres over all n_yaw yaws, into {output}/map/scan_localize.txt (scan.scan_localize_text: how well a planar
+    scanner tells the places of this map apart; `tsdf_scan_poses_tried` and `tsdf_scan_poses_recovered` in `stats`).  With
     cfg["tsdf"]["save_volume"] the fused volume goes to {output}/mesh/tsdf_volume.npz (TSDFVolume.save), and with
     cfg["tsdf"]["align"] = {enable, every, levels, huber, max_depth, min_count} (absent by default; rgbd mode only) every
     `every`-th frame of `stream` is aligned to the fused volume from its pose in `c2w_list` (localize.align_stream, in
@@ -1274,6 +1280,7 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
         fm = _floor.floor_config(ed.get("floor"), float(opt.get("voxel_size", 0.05)))
         if fm is not None and fm["plan"] and not (ed.get("plan") or {}).get("enable", False):
             raise ValueError("fuse_from_config: tsdf.esdf.floor.plan replans the route of tsdf.esdf.plan, which is off")
+    sc = _scan.scan_config(ed.get("scan")) if ed.get("enable", False) else None         # refused before anything is fused
     bound =opt.get("bound") or slam.cfg["mapping"]["bound"]
     min_weight = float(opt.get("min_weight", 1.0))
     vol, mesh = fuse_keyframes(slam.video, bound, float(opt.get("voxel_size", 0.05)), source=opt.get("source", "tracked"),
@@ -1499,6 +1506,15 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
                     stats.update(tsdf_floor_path_reachable=route["reachable"], tsdf_floor_path_length_m=route["length_m"])
                 print(f"TSDF floor path: reachable {route['reachable']!r}, length_m {route['length_m']!r}, "
                       f"{int(route['points'].shape[0])} points")
+        if sc is not None:
+            grid = field.occupancy_slice(sc["up_axis"], sc["height"], 0.0)
+            report = _scan.localize_poses(grid, _scan.planar_poses(nav_c2w, grid["axes"]), sc)
+            os.makedirs(f"{slam.output}/map", exist_ok=True)
+            with open(f"{slam.output}/map/scan_localize.txt", "w") as fh:
+                fh.write(_scan.scan_localize_text(report))
+            if stats is not None:
+                stats.update(tsdf_scan_poses_tried=report["poses_tried"], tsdf_scan_poses_recovered=report["poses_recovered"])
+            print("TSDF scan localisation: " + ", ".join(f"{k} {report[k]!r}" for k in _scan.SCAN_SUMMARY_ORDER))
     if opt.get("save_volume", False):
         vol.save(f"{slam.output}/mesh/tsdf_volume.npz")
     if merged is not None:

@@ -997,6 +997,51 @@ size_t gs_view_gain_lds_bytes(const int* box);
 int gs_view_gain(const unsigned char* state, int n0, int n1, int n2, const int* origins, int n_views, const int* dirs,
                  int n_rays, int range2, int max_unknown, const int* box, unsigned int* gain, gs_stream_t stream);
 
+/* ---- Range scans on a 2-D occupancy map and the exhaustive correlative scan match (no counterpart in the reference),
+ *      csrc/scan.hip; tests/scan_restatement.py restates it serially ----
+ *
+ * A map is cells u8 [n_u,n_v], n_u and n_v in [1, 1024], a map_server PGM's values read conservatively: 254 is free, 205
+ * is unknown, every other value is occupied.  A position is a cell (u, v), the cell's centre; the linear index of a cell
+ * is u * n_v + v.  Everything is integer.  All three entries return GS_ERR_INVALID_ARG for a size or a range outside what
+ * is stated here, a flag that is neither 0 nor 1 or a NULL pointer, before anything is launched or written; they enqueue
+ * on the stream and read nothing back.
+ *
+ * gs_scan_cast: a virtual range scanner, one ray per (pose, beam).  poses i32 [P,2] in cells, P >= 0 (P == 0 launches
+ *   nothing); dirs i32 [P,B,2], 1 <= B <= 4096, P * B <= 2^28, every component in [-GS_VIEW_MAX_DIR, GS_VIEW_MAX_DIR];
+ *   range2 in [1, 2 * 1023^2], the squared range in cells; stop_unknown 0 or 1.
+ *   The walk of one ray is the view-gain walk above on two axes: origin o, direction d, s_a = sign(d_a), w_a = |d_a|, one
+ *   step counter k_a per axis from 0.  The ray visits o first.  The next cell lies one step along s_a on the axis a with
+ *   w_a != 0 that minimises (2 k_a + 1) / (2 w_a), compared exactly: axis 1 beats axis 0 when
+ *   (2 k_1 + 1) * w_0 < (2 k_0 + 1) * w_1, a tie goes to axis 0 (both products stay below 2^31).  The ray ends, without
+ *   visiting that cell, when it lies outside the map or at a squared distance from o above range2; else k_a goes up by
+ *   one and the cell is visited.  A visited occupied cell ends the ray as a hit (kind 1); a visited unknown cell ends it
+ *   with kind 2 when stop_unknown is set and is passed through otherwise.  An occupied origin is a hit at range 0.  A
+ *   pose outside the map, an all-zero direction and a direction with a component out of range cast nothing (kind 0).
+ *   kind u8 [P,B]: 0 no return, 1 hit, 2 stopped at unknown.  hit i32 [P,B]: the linear index of the cell that ended the
+ *   ray (kind 1 or 2), else -1.  range_mc i32 [P,B]: floor(1000 * sqrt(du^2 + dv^2)) of that cell's offset (du, dv) from
+ *   the origin, in milli-cells, else -1.  Every element is written.
+ * gs_scan_field: the likelihood field of a map, cost u8 [n_u,n_v] = min(d2, cap), cap = R * R + 1, 1 <= R <= 15 (cap <=
+ *   226), d2 the exact squared cell distance to the nearest occupied cell of the map (unknown cells are no sites; a map
+ *   without an occupied cell is all cap).  Two separable band-limited passes, out[i] = min over |k| <= R of in[i + k] +
+ *   k * k, first along v from 0 at a site and cap elsewhere, then along u, each kept at min(., cap); a site further than
+ *   R cells along either axis is beyond the cap, so the result is exact.  Every element is written; no atomics.
+ * gs_scan_match: cost and cells [n_u,n_v] as above; offsets i32 [Y,B,2], 1 <= Y <= 1024, 1 <= B <= 4096: per yaw
+ *   hypothesis the cell offset (du, dv) of every beam's end point from the robot's cell; the translation window u0 <= u <
+ *   u0 + w_u, v0 <= v < v0 + w_v inside the map, w_u, w_v >= 1, Y * w_u * w_v <= 2^28; cap in [1, 226]; allow_unknown 0
+ *   or 1.  score u32 [Y,w_u,w_v], every element written: 0xffffffff when the robot's cell (u, v) is not free (with
+ *   allow_unknown an unknown cell counts as free), else the sum over the beams of cost[u + du, v + dv], where an end
+ *   point outside the map costs cap and an offset with a component outside [-32768, 32767] counts as outside the map.
+ *   best u64 [1]: the call resets it to all ones on the stream; it ends as the minimum, over the candidates whose score
+ *   is not 0xffffffff, of (score << 32) | linear index, linear index (y * w_u + i) * w_v + j for (y, u0 + i, v0 + j) --
+ *   reduced per wave, then by one 64-bit integer atomic min.  A minimum has no order: ties go to the lowest index and
+ *   every run gives the same bits.  All ones: no candidate may stand anywhere.                                          */
+int gs_scan_cast(const unsigned char* cells, int n_u, int n_v, const int* poses, int n_poses, const int* dirs, int n_beams,
+                 int range2, int stop_unknown, unsigned char* kind, int* hit, int* range_mc, gs_stream_t stream);
+int gs_scan_field(const unsigned char* cells, int n_u, int n_v, int R, unsigned char* cost, gs_stream_t stream);
+int gs_scan_match(const unsigned char* cost, const unsigned char* cells, int n_u, int n_v, const int* offsets, int n_yaws,
+                  int n_beams, int u0, int v0, int w_u, int w_v, int cap, int allow_unknown, unsigned int* score,
+                  unsigned long long* best, gs_stream_t stream);
+
 /* ---- frame preprocessing of the dataset readers (src/datasets.py:96-143, 565-605), csrc/frame_prep.hip ----
  *
  * Semantics: tests/frame_prep_restatement.py, bit for bit (cv2.remap / cv2.resize INTER_LINEAR on 8-bit data,
