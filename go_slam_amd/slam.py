@@ -208,14 +208,8 @@ class SLAM:
         """Fill in the poses of the non-keyframes, evaluate the trajectory and write the run's files (slam.py:289-370):
         checkpoints/go.ckpt, checkpoints/est_poses.npy, then submission.txt without ground truth or metrics_traj.txt with
         it, and the final mesh.  With cfg["tsdf"]["enable"] also mesh/tsdf_mesh.ply, the keyframe depth fused into a TSDF
-        (tsdf.fuse_from_config; this one also under only_tracking), and with cfg["tsdf"]["eval_depth"]["enable"] (keys
-        enable, every, save_images) metrics_tsdf_depth.txt: that volume raycast at the estimated poses against the sensor
-        depth, the means under `tsdf_*` keys of the returned statistics, and with cfg["tsdf"]["esdf"]["enable"]
-        metrics_tsdf_clearance.txt, the clearance of the estimated camera centres in that volume's distance field, and
-        with its `slice` key map/occupancy.pgm and .yaml, with its `plan` key map/path.txt, the collision-free route
-        between two points, by default from the last camera centre to the first (tsdf.fuse_from_config), and with
-        cfg["tsdf"]["merge"]["enable"] mesh/tsdf_merged_mesh.ply and metrics_tsdf_merge.txt, this run's volume registered to
-        and joined with the one an earlier run saved (tsdf_merge.join_volumes).  With cfg["tsdf"]["live"]["enable"] the
+        (this one also under only_tracking), and what the further keys of cfg["tsdf"] ask for, their values under `tsdf_*`
+        keys of the returned statistics (tsdf_run.fuse_from_config).  With cfg["tsdf"]["live"]["enable"] the
         running volume is brought to the final poses (LiveFusion.finish) and meshed into mesh/tsdf_live_mesh.ply, and
         `tsdf_live_refused` (keyframes re-fused over the run) and `tsdf_live_keyframes` join the statistics.  With
         cfg["render_eval"]["enable"] (keys enable, every, save_images) and a map, also metrics_render.txt: PSNR, SSIM and depth L1 of the map's renderings against the input

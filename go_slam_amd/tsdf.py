@@ -49,7 +49,8 @@ finds the doorways between them and the graph of both, and cfg["tsdf"]["esdf"]["
 (rooms.py; tests/rooms_restatement.py).
 
 tsdf_live.py keeps such a volume during a run, while the poses still move; it fuses through
-`keyframe_observations`, the rule `fuse_keyframes` applies per chunk.
+`keyframe_observations`, the rule `fuse_keyframes` applies per chunk.  tsdf_run.py is the end-of-run step that serves the
+cfg["tsdf"] keys above, one stage per key (`fuse_from_config`).
 """
 import math
 import os
@@ -64,7 +65,6 @@ from . import frontier as _frontier
 from . import localize as _localize
 from . import plan as _plan
 from . import rooms as _rooms
-from . import scan as _scan
 from . import tsdf_merge as _merge
 from . import tsdf_objects as _objects
 from . import tsdf_planes as _planes
@@ -1145,408 +1145,6 @@ def eval_tsdf_depth(vol, stream, c2w_list, intrinsics, every=5, out_path=None, s
 
 
 def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=None):
-    """`SLAM.terminate`'s TSDF step: with cfg["tsdf"]["enable"], fuse the run's keyframes, write
-    {output}/mesh/tsdf_mesh.ply and, with a readable meshing.gt_mesh_path and meshing.eval_rec, align and evaluate it
-    into {output}/metrics_tsdf_mesh.txt.  With cfg["tsdf"]["eval_depth"]["enable"] (keys enable, every, save_images;
-    absent by default) also raycast the fused volume at the poses `c2w_list` of the frames of `stream` and compare with
-    their sensor depth (eval_tsdf_depth) into {output}/metrics_tsdf_depth.txt, the means under `tsdf_*` keys of the dict
-    `stats`.  With cfg["tsdf"]["esdf"]["enable"] (keys enable, max_distance, save_volume, slice; absent by default)
-    also build the fused volume's distance field and write the clearance of the camera centres `c2w_list` into
-    {output}/metrics_tsdf_clearance.txt (trajectory_clearance; `tsdf_clearance_min_m`, `tsdf_clearance_inside` and
-    `tsdf_clearance_unknown` in `stats`), with save_volume {output}/mesh/tsdf_esdf.npz (dist, state, lo, voxel), and with
-    slice = {up_axis, height, robot_radius, known_fraction} the map {output}/map/occupancy.pgm and occupancy.yaml
-    (ESDF.save_map), and with plan = {enable, robot_radius, allow_unknown, snap, start, goal} (absent by default; start
-    and goal are world points or "last" / "first", the run's last and first camera centre, by default "last" and "first":
-    the way home) the route of ESDF.plan into {output}/map/path.txt (plan.path_text; `tsdf_path_reachable` and
-    `tsdf_path_length_m` in `stats`) and, with plan.straighten (a bool or {enable, window}; absent by default; another
-    value is refused before anything is fused), the route's waypoints by straight legs into {output}/map/path_straight.txt
-    beside it (plan.straight_path_text; `tsdf_path_straight_length_m` and `tsdf_path_waypoints` in `stats`), and, with
-    plan.follow = {enable, up_axis, heading, max_ticks, goal_tolerance and follow.Controller's keys; absent by default;
-    robot_radius and allow_unknown default to the plan's; a bad value is refused before anything is fused}, the closed-loop
-    drive of ESDF.follow between the route's two end cells into {output}/map/follow.txt (follow.follow_text;
-    `tsdf_follow_reached`, `tsdf_follow_ticks` and `tsdf_follow_min_clearance_m` in `stats`), and with
-    frontiers = {enable, robot_radius, min_cells, start, snap, order} (absent by
-    default; start is a world point or "last", the default) the frontier clusters of ESDF.frontiers into
-    {output}/map/frontiers.txt (frontier.frontiers_text) and, when ESDF.explore finds a goal, its route into
-    {output}/map/explore_path.txt (plan.path_text; `tsdf_frontier_cells`, `tsdf_frontier_clusters`,
-    `tsdf_unknown_fraction` and `tsdf_explore_reachable` in `stats`), and with next_view = {enable, camera, up_axis,
-    height, n_yaw, robot_radius, stride, snap, start, lam, min_gain_cells, min_solid_cells, max_unknown} (absent by
-    default; start is a world point or "last", the default) the pose of ESDF.next_view into {output}/map/next_view.txt
-    (view.next_view_text) and, when a view is found, its route into {output}/map/next_view_path.txt (plan.path_text;
-    `tsdf_next_view_found`, `tsdf_next_view_gain_m3` and `tsdf_next_view_candidates` in `stats`), and with rooms = {enable,
-    robot_radius, core_radius, min_core_m3, snap} (absent by default) the rooms and doorways of ESDF.rooms into
-    {output}/map/rooms.txt (rooms.rooms_text; `tsdf_rooms_found` and `tsdf_doors_found` in `stats`): with tsdf.objects on,
-    the file lists the room of every object (in the map frame when upright), with plan on, the rooms and doorways along
-    map/path.txt, and camera_room is the room of the last camera centre, moved by `snap` metres to a cell the robot may
-    be at; values that are no numbers with 0 <= robot_radius < core_radius (within max_distance), min_core_m3 > 0 and
-    snap >= 0 are refused before anything is fused or written, and with floor = {enable, up_axis, up_sign, height,
-    robot_radius, robot_height, step_height, plan} (absent by default) the drivable-floor map of ESDF.floor_map into
-    {output}/map/floor/occupancy.pgm and occupancy.yaml (save_map) and its areas into {output}/map/floor.txt
-    (floor.floor_text; `tsdf_floor_map_drivable_m2` and `tsdf_floor_map_unknown_m2` in `stats`), and with floor.plan (needs
-    plan on) the route of plan_on_map on that map between the end cells of map/path.txt, put on the floor by floor.lift,
-    into {output}/map/floor_path.txt (plan.path_text; `tsdf_floor_path_reachable` and `tsdf_floor_path_length_m` in
-    `stats`); a bad value is refused before anything is fused or written, and with scan = {up_axis, height, beams, fov_deg,
-    max_range, every, n_yaw, window_m} (absent by default; scan.scan_config) the occupancy slice at robot radius 0 of those
-    layers, on which a range scan is cast at every `every`-th pose of `c2w_list` whose cell is free (the camera centre on
-    the map's two axes, the yaw of the optical axis projected onto them) and found again by scan.localize_on_map within
-    window_m metres over all n_yaw yaws, into {output}/map/scan_localize.txt (scan.scan_localize_text: how well a planar
-    scanner tells the places of this map apart; `tsdf_scan_poses_tried` and `tsdf_scan_poses_recovered` in `stats`).  With
-    cfg["tsdf"]["save_volume"] the fused volume goes to {output}/mesh/tsdf_volume.npz (TSDFVolume.save), and with
-    cfg["tsdf"]["align"] = {enable, every, levels, huber, max_depth, min_count} (absent by default; rgbd mode only) every
-    `every`-th frame of `stream` is aligned to the fused volume from its pose in `c2w_list` (localize.align_stream, in
-    batches) into {output}/metrics_tsdf_align.txt (localize.align_text; `tsdf_align_moved_mean_m`,
-    `tsdf_align_moved_max_m`, `tsdf_align_moved_constrained_mean_m` -- the movement along the directions the surfaces in
-    view constrain, localize.constrained_movement -- and `tsdf_align_failed` in `stats`); another mode, or a missing
-    stream, is refused before anything is fused or written.  With cfg["tsdf"]["merge"] = {enable, volume, init, register,
-    levels, huber, min_count, save_volume} (absent by default) the volume an earlier run saved at `volume` is loaded, this
-    run's volume is registered to it from `init` (a 4 x 4 list, this run's world to the earlier run's; absent: the
-    identity; register false takes it as it is) and both are merged into a union volume (tsdf_merge.join_volumes) in the
-    earlier run's world: {output}/mesh/tsdf_merged_mesh.ply, {output}/metrics_tsdf_merge.txt (tsdf_merge.merge_text;
-    `tsdf_merge_overlap`, `tsdf_merge_rmse_m`, `tsdf_merge_moved_m` and `tsdf_merge_ok` in `stats`) and, with save_volume,
-    {output}/mesh/tsdf_merged_volume.npz.  A missing or unreadable file or a bad `init` is refused before anything is
-    fused, a failed registration before anything is written.  With cfg["tsdf"]["planes"] = {enable, bins, cone_deg, band,
-    max_planes, min_cells} (absent by default) the fused volume's dominant planes (TSDFVolume.find_planes) go to
-    {output}/metrics_tsdf_planes.txt (tsdf_planes.planes_text; `tsdf_planes_found` and `tsdf_floor_found` in `stats`), and
-    with cfg["tsdf"]["upright"] = {enable, up_hint, max_tilt_deg, up_axis, up_sign, heading, save_volume} (absent by
-    default; up_hint is a vector or "camera", minus the y column of the first pose of `c2w_list`, the default) the volume
-    is stood upright on its floor (tsdf_planes.floor_plane, TSDFVolume.upright) and the `esdf` key and everything under it
-    runs on the upright volume, in the map frame: `c2w_list` and explicit start and goal points are moved there first,
-    the transform world to map goes to {output}/map/upright.txt (tsdf_planes.transform_text) and, with save_volume, the
-    upright volume to {output}/mesh/tsdf_upright_volume.npz; the mesh, eval_depth, align and merge keep the run's own
-    volume, and a volume without a floor is refused before anything is written.  With cfg["tsdf"]["objects"] = {enable,
-    min_area_m2, cone_deg, band, min_cells} (absent by default) what stands on none of the structure planes
-    (tsdf_objects.structure_planes of the planes above -- found here when neither of the two keys is on -- with the floor
-    under up_hint first; TSDFVolume.find_objects on the run's own volume, up the floor's normal, or up_hint when there is
-    no floor) goes to {output}/map/objects.txt in the run's world (tsdf_objects.objects_text; with `upright` a second block
-    in the map frame; `tsdf_objects_found` and `tsdf_objects_on_floor` in `stats`); without an up hint it is refused before
-    anything is fused or written.  Returns the Mesh, or None when the key is absent or
-    disabled."""
-    opt = slam.cfg.get("tsdf") or {}
-    if not opt.get("enable", False):
-        return None
-    mg = opt.get("merge") or {}
-    earlier = None
-    if mg.get("enable", False):                             # refused before anything is fused or written
-        path = mg.get("volume")
-        if not path or not os.path.isfile(path):
-            raise ValueError(f"fuse_from_config: tsdf.merge.volume {path!r} is no file (TSDFVolume.save writes one)")
-        try:
-            earlier = TSDFVolume.load(path, device="cpu")
-        except Exception as e:
-            raise ValueError(f"fuse_from_config: tsdf.merge.volume {path!r} cannot be read as a saved volume: {e}") from None
-        merge_init = _merge.transforms34(np.eye(4) if mg.get("init") is None else np.asarray(mg["init"], np.float64),
-                                         "fuse_from_config: tsdf.merge.init")
-    al = opt.get("align") or {}
-    if al.get("enable", False):                             # refused before anything is fused or written
-        if slam.cfg.get("mode", "rgbd") != "rgbd":
-            raise ValueError(f"fuse_from_config: tsdf.align needs rgbd mode (mode is {slam.cfg.get('mode')!r}: "
-                             "no sensor depth to align)")
-        if stream is None or c2w_list is None:
-            raise ValueError("fuse_from_config: tsdf.align needs the stream and its camera-to-world poses")
-    pc, up, ob = opt.get("planes") or {}, opt.get("upright") or {}, opt.get("objects") or {}
-    up_hint = None
-    if pc.get("enable", False) or up.get("enable", False) or ob.get("enable", False):  # refused before anything is fused or written
-        up_hint = up.get("up_hint", "camera")
-        if isinstance(up_hint, str):
-            if up_hint != "camera":
-                raise ValueError(f"fuse_from_config: tsdf.upright.up_hint is a vector or 'camera' (got {up_hint!r})")
-            if c2w_list is not None and len(c2w_list) > 0:  # a camera's y axis points down
-                up_hint = (-torch.as_tensor(c2w_list[0])[:3, 1]).double().tolist()
-            elif up.get("enable", False):
-                raise ValueError("fuse_from_config: tsdf.upright.up_hint 'camera' needs the run's camera-to-world poses")
-            else:
-                up_hint = None
-        if up_hint is not None:
-            up_hint = _planes._vector3(up_hint, "fuse_from_config: tsdf.upright", "up_hint")
-        if up.get("heading") not in (None, "walls"):
-            raise ValueError(f"fuse_from_config: tsdf.upright.heading must be absent or 'walls' (got {up.get('heading')!r})")
-    ob_args = {k: ob[k] for k in ("cone_deg", "band", "min_cells") if k in ob}
-    if ob.get("enable", False):                             # refused before anything is fused or written
-        if up_hint is None:
-            raise ValueError("fuse_from_config: tsdf.objects needs to know where up is: the run's camera-to-world poses or "
-                             "a vector tsdf.upright.up_hint")
-        _objects.find_arguments("fuse_from_config: tsdf.objects", float(opt.get("voxel_size", 0.05)), [], up_hint, **ob_args)
-        _objects.structure_planes([], None, ob.get("min_area_m2", 2.0))
-    ed = opt.get("esdf") or {}
-    rm = (ed.get("rooms") or {}) if ed.get("enable", False) else {}
-    if rm.get("enable", False):                             # refused before anything is fused or written
-        rm_args = _rooms.config_arguments(rm, float(opt.get("voxel_size", 0.05)), ed.get("max_distance"))
-    pl_window = pl_follow = None
-    if ed.get("enable", False) and (ed.get("plan") or {}).get("enable", False):          # refused before anything is fused
-        pl_window = _plan.straighten_config(ed["plan"].get("straighten"), "fuse_from_config: tsdf.esdf.plan.straighten")
-        pl_follow = _follow.follow_config(ed["plan"].get("follow"), "fuse_from_config: tsdf.esdf.plan.follow")
-    fm = None
-    if ed.get("enable", False):                             # refused before anything is fused or written
-        fm = _floor.floor_config(ed.get("floor"), float(opt.get("voxel_size", 0.05)))
-        if fm is not None and fm["plan"] and not (ed.get("plan") or {}).get("enable", False):
-            raise ValueError("fuse_from_config: tsdf.esdf.floor.plan replans the route of tsdf.esdf.plan, which is off")
-    sc = _scan.scan_config(ed.get("scan")) if ed.get("enable", False) else None         # refused before anything is fused
-    bound =opt.get("bound") or slam.cfg["mapping"]["bound"]
-    min_weight = float(opt.get("min_weight", 1.0))
-    vol, mesh = fuse_keyframes(slam.video, bound, float(opt.get("voxel_size", 0.05)), source=opt.get("source", "tracked"),
-                               trunc=opt.get("truncation"), min_weight=min_weight)
-    merged = None
-    if earlier is not None:                                 # a failed registration is refused before anything is written
-        for name in ("tsdf", "weight", "colors"):
-            setattr(earlier, name, getattr(earlier, name).to(vol.device))
-        earlier.device = vol.device
-        merged = _merge.join_volumes([earlier, vol], [None, merge_init[0]], register=mg.get("register", True),
-                                     min_weight=min_weight, levels=mg.get("levels", _merge.DEFAULT_LEVELS),
-                                     huber=mg.get("huber", 0.5), min_count=mg.get("min_count", 64))
-    planes = floor = upright = objects = None
-    if pc.get("enable", False) or up.get("enable", False) or ob.get("enable", False):
-        # a missing floor is refused before anything is written
-        planes = vol.find_planes(min_weight=min_weight,
-                                 **{k: pc[k] for k in ("bins", "cone_deg", "band", "max_planes", "min_cells") if k in pc})
-        if up_hint is not None:
-            floor = _planes.floor_plane(planes, up_hint, up.get("max_tilt_deg", 35.0))
-        if up.get("enable", False):
-            if floor is None:
-                raise ValueError(f"fuse_from_config: tsdf.upright found no floor among the volume's {len(planes)} planes "
-                                 f"within {up.get('max_tilt_deg', 35.0)} degrees of up_hint {up_hint.tolist()}")
-            upright = _planes.upright_volume(vol, floor, None, up.get("up_axis", 2), up.get("up_sign", 1), up.get("heading"),
-                                             planes=planes)
-        if ob.get("enable", False):                         # on the run's own volume: resampling loses the floor's samples
-            structure, _ = _objects.structure_planes(planes, floor, ob.get("min_area_m2", 2.0))
-            objects = vol.find_objects(structure, up=up_hint if floor is None else floor, min_weight=min_weight, **ob_args)
-    os.makedirs(f"{slam.output}/mesh", exist_ok=True)
-    mesh.export(f"{slam.output}/mesh/tsdf_mesh.ply")
-    if pc.get("enable", False):
-        with open(f"{slam.output}/metrics_tsdf_planes.txt", "w") as fh:
-            fh.write(_planes.planes_text(planes, floor))
-        if stats is not None:
-            stats.update(tsdf_planes_found=len(planes), tsdf_floor_found=floor is not None)
-        print(f"TSDF planes: {len(planes)} found, floor " + ("none" if floor is None else
-                                                             f"normal {floor['normal'].tolist()!r} offset {floor['offset']!r}"))
-    nav_vol, nav_c2w, nav_point = vol, c2w_list, (lambda point: point)
-    if upright is not None:                                 # the navigation keys below run in the map frame
-        nav_vol, to_map = upright
-        if c2w_list is not None:
-            nav_c2w = _planes.moved_poses(to_map, c2w_list)
-        nav_point = lambda point: point if isinstance(point, str) else _planes.moved_point(to_map, point)  # noqa: E731
-        os.makedirs(f"{slam.output}/map", exist_ok=True)
-        with open(f"{slam.output}/map/upright.txt", "w") as fh:
-            fh.write(_planes.transform_text(to_map))
-        if up.get("save_volume", False):
-            nav_vol.save(f"{slam.output}/mesh/tsdf_upright_volume.npz")
-    if objects is not None:
-        os.makedirs(f"{slam.output}/map", exist_ok=True)
-        with open(f"{slam.output}/map/objects.txt", "w") as fh:
-            fh.write(_objects.objects_text(objects.boxes,
-                                           None if upright is None else _objects.moved_objects(objects, upright[1])))
-        on_floor = 0 if floor is None else sum(1 for b in objects.boxes if 0 in b["touches"])
-        if stats is not None:
-            stats.update(tsdf_objects_found=len(objects.boxes), tsdf_objects_on_floor=on_floor)
-        print(f"TSDF objects: {len(objects.boxes)} found in {objects.n_clusters} clusters, {on_floor} on the floor")
-    ev =opt.get("eval_depth") or {}
-    if ev.get("enable", False):
-        if stream is None or c2w_list is None:
-            raise ValueError("fuse_from_config: tsdf.eval_depth needs the stream and its camera-to-world poses")
-        res = eval_tsdf_depth(vol, stream, c2w_list, (slam.video.intrinsics[0] * 8).cpu().tolist(),
-                              every=ev.get("every", 5), out_path=f"{slam.output}/metrics_tsdf_depth.txt",
-                              save_images=ev.get("save_images", False), min_weight=min_weight,
-                              metric_depth=slam.mode == "rgbd")
-        if stats is not None:
-            stats.update({f"tsdf_{k}": res[k] for k in DEPTH_REPORT_ORDER})
-        print("TSDF depth: " + ", ".join(f"{k} {res[k]!r}" for k in DEPTH_REPORT_ORDER))
-    if ed.get("enable", False):
-        if c2w_list is None:
-            raise ValueError("fuse_from_config: tsdf.esdf needs the run's camera-to-world poses")
-        field = nav_vol.esdf(ed.get("max_distance"), min_weight=min_weight)
-        res = trajectory_clearance(field, nav_c2w, out_path=f"{slam.output}/metrics_tsdf_clearance.txt")
-        if stats is not None:
-            stats.update(tsdf_clearance_min_m=res["clearance_min_m"], tsdf_clearance_inside=res["n_inside"],
-                         tsdf_clearance_unknown=res["n_unknown"])
-        print("TSDF clearance: " + ", ".join(f"{k} {res[k]!r}" for k in CLEARANCE_REPORT_ORDER))
-        if ed.get("save_volume", False):
-            np.savez(f"{slam.output}/mesh/tsdf_esdf.npz", dist=field.dist.cpu().numpy(), state=field.state.cpu().numpy(),
-                     lo=field.lo, voxel=field.voxel)
-        sl = ed.get("slice")
-        if sl:
-            field.save_map(f"{slam.output}/map", sl["up_axis"], sl["height"], sl.get("robot_radius", 0.0),
-                           sl.get("known_fraction", 0.5))
-        pl = ed.get("plan") or {}
-        planned = None
-        if pl.get("enable", False):
-            ends = []
-            for end in (nav_point(pl.get("start", "last")), nav_point(pl.get("goal", "first"))):
-                if isinstance(end, str) and end in ("last", "first"):
-                    if len(c2w_list) == 0:
-                        raise ValueError("fuse_from_config: tsdf.esdf.plan needs a camera pose for 'last' / 'first'")
-                    end = torch.as_tensor(nav_c2w[-1 if end == "last" else 0])[:3, 3]
-                ends.append(end)
-            res = field.plan(ends[0], ends[1], robot_radius=pl.get("robot_radius", 0.0),
-                             allow_unknown=pl.get("allow_unknown", False), snap=pl.get("snap", 0.0),
-                             **({} if pl_window is None else {"straighten": True, "window": pl_window}))
-            os.makedirs(f"{slam.output}/map", exist_ok=True)
-            with open(f"{slam.output}/map/path.txt", "w") as fh:
-                fh.write(_plan.path_text(res))
-            if stats is not None:
-                stats.update(tsdf_path_reachable=res["reachable"], tsdf_path_length_m=res["length_m"])
-            if pl_window is not None:
-                with open(f"{slam.output}/map/path_straight.txt", "w") as fh:
-                    fh.write(_plan.straight_path_text(res))
-                if stats is not None:
-                    stats.update(tsdf_path_straight_length_m=res["straight_length_m"],
-                                 tsdf_path_waypoints=int(res["waypoints"].shape[0]))
-                print(f"TSDF straightened path: length_m {res['straight_length_m']!r}, min_clearance_m "
-                      f"{res['straight_min_clearance_m']!r}, {int(res['waypoints'].shape[0])} waypoints")
-            print(f"TSDF path: reachable {res['reachable']!r}, length_m {res['length_m']!r}, "
-                  f"min_clearance_m {res['min_clearance_m']!r}, {int(res['cells'].shape[0])} points")
-            planned = res
-            if pl_follow is not None:
-                drove = _follow.no_drive()
-                if res["start_cell"] is not None and res["goal_cell"] is not None:
-                    # between the cells the route was planned between: camera centres usually sit in cells that do not pass
-                    lo = torch.tensor(field.lo, dtype=torch.float64)
-                    drive_args = dict(pl_follow[1])
-                    drive_args.setdefault("robot_radius", pl.get("robot_radius", 0.0))
-                    drive_args.setdefault("allow_unknown", pl.get("allow_unknown", False))
-                    drove = field.follow(lo + torch.tensor(res["start_cell"], dtype=torch.float64) * field.voxel,
-                                         lo + torch.tensor(res["goal_cell"], dtype=torch.float64) * field.voxel,
-                                         pl_follow[0], **drive_args)
-                with open(f"{slam.output}/map/follow.txt", "w") as fh:
-                    fh.write(_follow.follow_text(drove))
-                if stats is not None:
-                    stats.update(tsdf_follow_reached=drove["reached"], tsdf_follow_ticks=drove["ticks"],
-                                 tsdf_follow_min_clearance_m=drove["min_clearance_m"])
-                print(f"TSDF follow: reached {drove['reached']!r}, ticks {drove['ticks']!r}, length_m "
-                      f"{drove['length_m']!r}, min_clearance_m {drove['min_clearance_m']!r}, stops {drove['stops']!r}")
-        fr = ed.get("frontiers") or {}
-        if fr.get("enable", False):
-            start = nav_point(fr.get("start", "last"))
-            if isinstance(start, str):
-                if start != "last":
-                    raise ValueError(f"fuse_from_config: tsdf.esdf.frontiers.start is a world point or 'last' (got {start!r})")
-                if len(c2w_list) == 0:
-                    raise ValueError("fuse_from_config: tsdf.esdf.frontiers needs a camera pose for 'last'")
-                start = torch.as_tensor(nav_c2w[-1])[:3, 3]
-            res = field.explore(start, robot_radius=fr.get("robot_radius", 0.0), snap=fr.get("snap", 0.0),
-                                min_cells=fr.get("min_cells", 1), order=fr.get("order", "nearest"))
-            report = _frontier.summary(res["clusters"], res["cluster"])
-            os.makedirs(f"{slam.output}/map", exist_ok=True)
-            with open(f"{slam.output}/map/frontiers.txt", "w") as fh:
-                fh.write(_frontier.frontiers_text(report))
-            if res["reachable"]:
-                with open(f"{slam.output}/map/explore_path.txt", "w") as fh:
-                    fh.write(_plan.path_text(res))
-            if stats is not None:
-                stats.update(tsdf_frontier_cells=report["n_frontier"], tsdf_frontier_clusters=report["n_clusters"],
-                             tsdf_unknown_fraction=report["unknown_fraction"], tsdf_explore_reachable=res["reachable"])
-            print(f"TSDF frontiers: {report['n_frontier']} cells in {report['n_clusters']} clusters, {report['n_kept']} "
-                  f"kept, {report['n_reachable']} reachable, unknown_fraction {report['unknown_fraction']!r}, "
-                  f"chosen {report['cluster']!r}")
-        nv = ed.get("next_view") or {}
-        if nv.get("enable", False):
-            start = nav_point(nv.get("start", "last"))
-            if isinstance(start, str):
-                if start != "last":
-                    raise ValueError(f"fuse_from_config: tsdf.esdf.next_view.start is a world point or 'last' (got {start!r})")
-                if len(c2w_list) == 0:
-                    raise ValueError("fuse_from_config: tsdf.esdf.next_view needs a camera pose for 'last'")
-                start = torch.as_tensor(nav_c2w[-1])[:3, 3]
-            res = field.next_view(start, nv["camera"], nv["up_axis"], nv["height"], n_yaw=nv.get("n_yaw", 8),
-                                  robot_radius=nv.get("robot_radius", 0.0), stride=nv.get("stride", 4),
-                                  snap=nv.get("snap", 0.0), max_unknown=nv.get("max_unknown", 0),
-                                  min_gain_cells=nv.get("min_gain_cells", 1),
-                                  min_solid_cells=nv.get("min_solid_cells", 0), lam=nv.get("lam", 0.0))
-            os.makedirs(f"{slam.output}/map", exist_ok=True)
-            with open(f"{slam.output}/map/next_view.txt", "w") as fh:
-                fh.write(_view.next_view_text(res))
-            if res["view_cell"] is not None:
-                with open(f"{slam.output}/map/next_view_path.txt", "w") as fh:
-                    fh.write(_plan.path_text(res))
-            if stats is not None:
-                stats.update(tsdf_next_view_found=res["view_cell"] is not None, tsdf_next_view_gain_m3=res["gain_m3"],
-                             tsdf_next_view_candidates=res["n_candidates"])
-            print(f"TSDF next view: cell {res['view_cell']!r}, yaw {res['yaw']!r}, gain_m3 {res['gain_m3']!r}, "
-                  f"{res['n_candidates']} candidates, {res['n_qualified']} qualified")
-        if rm.get("enable", False):
-            res = field.rooms(robot_radius=rm_args["robot_radius"], core_radius=rm_args["core_radius"],
-                              min_core_m3=rm_args["min_core_m3"])
-            boxes = None
-            if objects is not None:                         # in the frame of the field
-                boxes = objects.boxes if upright is None else _objects.moved_objects(objects, upright[1])
-            here = None
-            if len(c2w_list) > 0:
-                here = _rooms.room_of_point(res, torch.as_tensor(nav_c2w[-1])[:3, 3].double().tolist(), rm_args["snap"])
-            along = res.rooms_along(planned["cells"]) if planned is not None and planned["reachable"] else None
-            report = _rooms.summary(res, boxes, along, here)
-            os.makedirs(f"{slam.output}/map", exist_ok=True)
-            with open(f"{slam.output}/map/rooms.txt", "w") as fh:
-                fh.write(_rooms.rooms_text(report))
-            if stats is not None:
-                stats.update(tsdf_rooms_found=report["n_rooms"], tsdf_doors_found=report["n_doors"])
-            print(f"TSDF rooms: {report['n_rooms']} rooms and {report['n_doors']} doorways over {report['n_open']} open "
-                  f"cells, {report['n_core']} of them core, camera in room {report['camera_room']!r}")
-        if fm is not None:
-            grid = field.floor_map(fm["up_axis"], fm["height"], fm["robot_radius"], fm["robot_height"], fm["step_height"],
-                                   fm["up_sign"])
-            report = _floor.summary(grid)
-            save_map(f"{slam.output}/map/floor", grid)      # save_map's file names are fixed: a directory of its own
-            with open(f"{slam.output}/map/floor.txt", "w") as fh:
-                fh.write(_floor.floor_text(report))
-            if stats is not None:
-                stats.update(tsdf_floor_map_drivable_m2=report["drivable_m2"], tsdf_floor_map_unknown_m2=report["unknown_m2"])
-            print("TSDF floor map: " + ", ".join(f"{k} {report[k]!r}" for k in _floor.FLOOR_REPORT_ORDER))
-            if fm["plan"]:
-                route = {"reachable": False, "length_m": math.inf, "points": np.zeros((0, 3))}
-                if planned["start_cell"] is not None and planned["goal_cell"] is not None:
-                    # between the cells the 3-D route was planned between, as plan.follow does
-                    u, v = grid["axes"]
-                    ends = [(field.lo[u] + cell[u] * field.voxel, field.lo[v] + cell[v] * field.voxel)
-                            for cell in (planned["start_cell"], planned["goal_cell"])]
-                    res = _plan.plan_on_map(grid, ends[0], ends[1])
-                    if res["reachable"]:
-                        route = {"reachable": True, "length_m": res["length_m"], "points": _floor.lift(grid, res["cells"])}
-                route["min_clearance_m"] = math.nan         # the floor map has no clearance field
-                with open(f"{slam.output}/map/floor_path.txt", "w") as fh:
-                    fh.write(_plan.path_text(route))
-                if stats is not None:
-                    stats.update(tsdf_floor_path_reachable=route["reachable"], tsdf_floor_path_length_m=route["length_m"])
-                print(f"TSDF floor path: reachable {route['reachable']!r}, length_m {route['length_m']!r}, "
-                      f"{int(route['points'].shape[0])} points")
-        if sc is not None:
-            grid = field.occupancy_slice(sc["up_axis"], sc["height"], 0.0)
-            report = _scan.localize_poses(grid, _scan.planar_poses(nav_c2w, grid["axes"]), sc)
-            os.makedirs(f"{slam.output}/map", exist_ok=True)
-            with open(f"{slam.output}/map/scan_localize.txt", "w") as fh:
-                fh.write(_scan.scan_localize_text(report))
-            if stats is not None:
-                stats.update(tsdf_scan_poses_tried=report["poses_tried"], tsdf_scan_poses_recovered=report["poses_recovered"])
-            print("TSDF scan localisation: " + ", ".join(f"{k} {report[k]!r}" for k in _scan.SCAN_SUMMARY_ORDER))
-    if opt.get("save_volume", False):
-        vol.save(f"{slam.output}/mesh/tsdf_volume.npz")
-    if merged is not None:
-        joined, transforms, reports = merged
-        joined.extract_mesh(min_weight).export(f"{slam.output}/mesh/tsdf_merged_mesh.ply")
-        res = _merge.merge_report(reports[1])
-        with open(f"{slam.output}/metrics_tsdf_merge.txt", "w") as fh:
-            fh.write(_merge.merge_text(res, transforms[1]))
-        if mg.get("save_volume", False):
-            joined.save(f"{slam.output}/mesh/tsdf_merged_volume.npz")
-        if stats is not None:
-            stats.update(tsdf_merge_overlap=res["overlap"], tsdf_merge_rmse_m=res["rmse_m"],
-                         tsdf_merge_moved_m=res["moved_m"], tsdf_merge_ok=bool(res["ok"]))
-        print("TSDF merge: " + ", ".join(f"{k} {res[k]!r}" for k in _merge.MERGE_REPORT_ORDER))
-    if al.get("enable", False):
-        res = _localize.align_stream(vol, stream, c2w_list, (slam.video.intrinsics[0] * 8).cpu().tolist(),
-                                     every=al.get("every", 5), out_path=f"{slam.output}/metrics_tsdf_align.txt",
-                                     levels=al.get("levels", _localize.DEFAULT_LEVELS), huber=al.get("huber", 0.5),
-                                     max_depth=al.get("max_depth", math.inf), min_count=al.get("min_count", 64),
-                                     min_weight=min_weight)
-        if stats is not None:
-            stats.update(tsdf_align_moved_mean_m=res["moved_mean_m"], tsdf_align_moved_max_m=res["moved_max_m"],
-                         tsdf_align_moved_constrained_mean_m=res["moved_constrained_mean_m"],
-                         tsdf_align_failed=res["n_failed"])
-        print("TSDF align: " + ", ".join(f"{k} {res[k]!r}" for k in _localize.ALIGN_REPORT_ORDER))
-    meshing = slam.cfg.get("meshing") or {}
-    gt_path = meshing.get("gt_mesh_path") or ""
-    if meshing.get("eval_rec") and gt_path.find(".ply") > -1 and os.path.exists(gt_path) and len(mesh.faces) > 0:
-        from .neus.mesh import load_mesh
-        from .neus.mesh_eval import align_mesh, eval_mesh
-        gt_mesh = load_mesh(gt_path)
-        aligned = align_mesh(mesh.copy(), gt_mesh, threshold=0.1, trans_init=trans_init)
-        eval_mesh(aligned, gt_mesh, N3d=meshing.get("n_points_to_eval", 200000),
-                  dist_th=meshing.get("mesh_threshold_to_eval", 0.05), out_path=f"{slam.output}/metrics_tsdf_mesh.txt")
-    return mesh
+    """`SLAM.terminate`'s TSDF step, `tsdf_run.fuse_from_config` (which imports this module: hence not at the top)."""
+    from .tsdf_run import fuse_from_config as run
+    return run(slam, stream=stream, trans_init=trans_init, c2w_list=c2w_list, stats=stats)
