@@ -116,6 +116,10 @@ SIGNATURES = {
     "gs_scan_cast": (c_int, [_P, c_int, c_int, _P, c_int, _P] + [c_int] * 3 + [_P, _P, _P, _P]),
     "gs_scan_field": (c_int, [_P, c_int, c_int, c_int, _P, _P]),
     "gs_scan_match": (c_int, [_P, _P, c_int, c_int, _P] + [c_int] * 8 + [_P, _P, _P]),
+    "gs_mcl_move": (c_int, [_P, c_int, _P, c_int, _P] + [c_int] * 5 + [_P, _P]),
+    "gs_mcl_weigh": (c_int, [_P, _P, c_int, c_int, _P, c_int, _P] + [c_int] * 4 + [_P, _P, _P]),
+    "gs_mcl_estimate": (c_int, [_P, _P, c_int, _P, c_int, _P, c_int, _P, _P, _P, _P]),
+    "gs_mcl_resample": (c_int, [_P, _P, c_int, ctypes.c_uint64, ctypes.c_uint64, _P, _P]),
     "gs_frame_prep_color": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P]),
     "gs_frame_prep_depth": (c_int, [_P, c_int, c_float, c_int, c_int, c_int, c_int, _P]),
     "gs_cvx_upsample":(c_int, [_P] * 4 + [c_int] * 4 + [_P]),

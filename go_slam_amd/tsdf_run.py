@@ -20,6 +20,7 @@ from . import localize as _localize
 from . import plan as _plan
 from . import rooms as _rooms
 from . import scan as _scan
+from . import mcl as _mcl
 from . import tsdf as _tsdf
 from . import tsdf_merge as _merge
 from . import tsdf_objects as _objects
@@ -320,7 +321,7 @@ def write_mesh_eval(run, meshing):
 
 
 def write_esdf(run, ed):
-    """tsdf.esdf = {enable, max_distance, save_volume, slice, plan, frontiers, next_view, rooms, floor, scan} (absent by
+    """tsdf.esdf = {enable, max_distance, save_volume, slice, plan, frontiers, next_view, rooms, floor, scan, mcl} (absent by
     default): the distance field of the volume (TSDFVolume.esdf) and the clearance of the camera centres in it go to
     metrics_tsdf_clearance.txt (tsdf.trajectory_clearance), with save_volume the field to mesh/tsdf_esdf.npz (dist,
     state, lo, voxel), and with slice = {up_axis, height, robot_radius 0, known_fraction 0.5} the map of that slab to
@@ -531,6 +532,26 @@ def write_scan(run, sc):
                "TSDF scan localisation: " + ", ".join(f"{k} {report[k]!r}" for k in _scan.SCAN_SUMMARY_ORDER))
 
 
+def check_mcl(run):
+    """tsdf.esdf.mcl = {up_axis, height, beams 360, fov_deg 360, max_range, every 5, particles 2048, headings 360,
+    drift {scale 1, yaw_deg_per_m 0}, seed 0} (absent by default, on whenever present; mcl.mcl_config): on the occupancy
+    slice at robot radius 0 of those layers a particle filter (mcl.track_on_map) follows every `every`-th pose of the
+    run (scan.planar_poses) from a scan cast at each and the odometry between consecutive ones, stretched and turned by
+    `drift`, and relocalises by the exhaustive match when it reports itself lost, into map/mcl.txt (mcl.mcl_text).
+    stats: tsdf_mcl_ticks, tsdf_mcl_max_error_m, tsdf_mcl_relocalized.  Refuses before the fusion an unknown key and a
+    bad value."""
+    return _mcl.mcl_config(run.esdf.get("mcl")) if run.esdf else None
+
+
+def write_mcl(run, mc):
+    grid = run.field.occupancy_slice(mc["up_axis"], mc["height"], 0.0)
+    report = _mcl.track_poses(grid, _scan.planar_poses(run.nav_c2w, grid["axes"]), mc)
+    run.write("map/mcl.txt", _mcl.mcl_text(report))
+    run.report(dict(tsdf_mcl_ticks=report["ticks"], tsdf_mcl_max_error_m=report["max_error_m"],
+                    tsdf_mcl_relocalized=report["relocalized"]),
+               "TSDF particle filter: " + ", ".join(f"{k} {report[k]!r}" for k in _mcl.MCL_SUMMARY_ORDER))
+
+
 # ---- the driver -------------------------------------------------------------------------------------------------------
 def fuse(run):
     """The fusion: tsdf = {enable, bound (mapping.bound), voxel_size 0.05, source "tracked", truncation, min_weight 1}
@@ -558,13 +579,14 @@ def fuse_from_config(slam, stream=None, trans_init=None, c2w_list=None, stats=No
     upright, planes, objects = check_upright(run), check_planes(run), check_objects(run)
     eval_depth, rooms, plan = check_eval_depth(run), check_rooms(run), check_plan(run)
     frontiers, next_view, floor, scan = check_frontiers(run), check_next_view(run), check_floor(run), check_scan(run)
+    mcl = check_mcl(run)
     fuse(run)
     stages = [(join_merge, merge), (find_planes, run.level), (stand_upright, upright),
               (find_objects, objects),                         # what may still refuse; from here on files are written
               (write_mesh, True), (write_planes, planes), (write_upright, upright), (write_objects, objects),
               (write_eval_depth, eval_depth), (write_esdf, run.esdf or None), (write_plan, plan),
               (write_frontiers, frontiers), (write_next_view, next_view), (write_rooms, rooms), (write_floor, floor),
-              (write_scan, scan), (write_volume, opt.get("save_volume") or None), (write_merge, merge),
+              (write_scan, scan), (write_mcl, mcl), (write_volume, opt.get("save_volume") or None), (write_merge, merge),
               (write_align, align), (write_mesh_eval, slam.cfg.get("meshing") or None)]
     for stage, args in stages:                                 # None: the stage's key is off
         if args is not None:

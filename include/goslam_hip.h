@@ -1042,6 +1042,62 @@ int gs_scan_match(const unsigned char* cost, const unsigned char* cells, int n_u
                   int n_beams, int u0, int v0, int w_u, int w_v, int cap, int allow_unknown, unsigned int* score,
                   unsigned long long* best, gs_stream_t stream);
 
+/* ---- Monte Carlo localisation on a 2-D occupancy map: particles moved by odometry, weighed against a range scan on the
+ *      likelihood field of gs_scan_field, resampled (no counterpart in the reference), csrc/mcl.hip;
+ *      tests/mcl_restatement.py restates it serially ----
+ *
+ * The map is the scan block's: cells and cost u8 [n_u,n_v], n_u and n_v in [1, 1024], 254 free, 205 unknown, anything else
+ * occupied.  Everything is integer.  particles i32 [N,3], 0 <= N <= GS_MCL_MAX_PARTICLES (N == 0 launches nothing), one
+ * row (x, y, h) per particle -- interleaved, because the weigh kernel gives a wave to a particle and reads the row as three
+ * consecutive scalars: x, y in milli-cells, 0 <= x < 1000 n_u, 0 <= y < 1000 n_v, the particle's cell is (x / 1000,
+ * y / 1000); h a heading index in [0, H), 1 <= H <= 1024, for the yaw 2 pi h / H (yaw 0 along +u, positive toward +v).
+ * rot i32 [H,2]: rint(2^14 (cos, sin)(2 pi h / H)), every |component| <= 2^14.  All four entries return
+ * GS_ERR_INVALID_ARG for a size or a value outside what is stated here, a flag that is neither 0 nor 1, a NULL pointer, a
+ * 64-bit array that is not 8-byte aligned or outputs that alias inputs where that is refused, before anything is launched
+ * or written; they enqueue on the stream and read nothing back.
+ *
+ * gs_mcl_move: the odometry step (df, dl, dh) -- forward and left in milli-cells, heading steps, each |.| <= 2^20 -- plus
+ *   the particle's own noise i32 [N,3] (each |.| <= 2^20).  With f = df + n0, l = dl + n1, (c, s) = rot[h] of the old
+ *   heading, in i64 (|f c| <= 2^21 * 2^14: far inside):
+ *     x' = clamp(x + ((f c - l s + 8192) >> 14), 0, 1000 n_u - 1),  y' = clamp(y + ((f s + l c + 8192) >> 14), 0, 1000 n_v - 1)
+ *     h' = (h + dh + n2) mod H, non-negative;  >> is the arithmetic shift (floor).
+ *   out i32 [N,3] may be the particles themselves; any other overlap is refused.  An h outside [0, H) (outside the
+ *   contract) is wrapped into it for the table read.
+ * gs_mcl_weigh: ends i32 [H,B,2], 1 <= B <= 4096, 8-byte aligned: per heading the end point (ex, ey) of every beam in
+ *   milli-cells from the robot; cap in [1, 226]; allow_unknown 0 or 1.  S u32 [N], every element written: 0xffffffff when
+ *   the particle's cell is not free (with allow_unknown an unknown cell counts as free; so does a particle outside the
+ *   map or with h outside [0, H)), else the sum over the beams of cost[floor((x + ex) / 1000), floor((y + ey) / 1000)] --
+ *   the floor of a negative sum goes down, not toward zero --, where an end point outside the map or with |ex| or |ey| >
+ *   4 000 000 costs cap.  S <= 4096 * 226 < 2^20.  best u64 [1]: the call resets it to all ones on the stream; it ends as
+ *   the minimum over the standing particles of (S << 32) | p, all ones when none stands -- reduced per workgroup, then by
+ *   one 64-bit integer atomic min.  A minimum has no order: ties go to the lowest p and every run gives the same bits.
+ * gs_mcl_estimate: S as above, lut u32 [L], 1 <= L <= 65536, every entry <= 2^20.  With S_min the smallest S that is not
+ *   0xffffffff: w u32 [N] = lut[S - S_min] where the particle stands and S - S_min < L, else 0; cum u64 [N] the inclusive
+ *   prefix sum of w; stats u64 [GS_MCL_STATS]:
+ *     0 W = sum w    1 sum w^2    2 the particles standing    3 those with w > 0    4 the key `best` of gs_mcl_weigh
+ *     5 sum w x      6 sum w y    7 sum w c    8 sum w s  (c, s) = rot[h], two's complement i64
+ *     9, 10 sum w (x^2 >> 20), sum w (x^2 & 0xfffff)    11, 12 the same of y^2    13, 14 the same of x y    15 zero
+ *   so that sum w x^2 = (stats[9] << 20) + stats[10] exactly.  Bounds: w <= 2^20, N <= 2^16, x, y < 1 024 000 < 2^20,
+ *   |c|, |s| <= 2^14: W <= 2^36; sum w^2, sum w x, sum w y < 2^56; |sum w c| <= 2^50; x^2 < 2^40, so both of its parts
+ *   are below 2^20 and each of the six sums is below 2^56: every word stays below 2^57.  Integer sums have no order:
+ *   every run gives the same bits.  One workgroup.  N == 0 writes nothing.
+ * gs_mcl_resample: systematic resampling.  cum u64 [N] as above with W = cum[N - 1] in [1, 2^36] and 0 <= q < W given by
+ *   the host (W == 0 is refused).  New particle j is a copy of the old particle i, the smallest i with cum[i] * N >
+ *   j * W + q (both sides below 2^52); i = N - 1 when a cum that does not end in W leaves none.  out i32 [N,3] must share
+ *   no byte with the particles.                                                                                        */
+#define GS_MCL_MAX_PARTICLES 65536
+#define GS_MCL_STATS 16
+int gs_mcl_move(const int* particles, int n, const int* rot, int n_headings, const int* noise, int df, int dl, int dh,
+                int n_u, int n_v, int* out, gs_stream_t stream);
+int gs_mcl_weigh(const unsigned char* cost, const unsigned char* cells, int n_u, int n_v, const int* particles, int n,
+                 const int* ends, int n_headings, int n_beams, int cap, int allow_unknown, unsigned int* S,
+                 unsigned long long* best, gs_stream_t stream);
+int gs_mcl_estimate(const unsigned int* S, const int* particles, int n, const int* rot, int n_headings,
+                    const unsigned int* lut, int n_lut, unsigned int* w, unsigned long long* cum,
+                    unsigned long long* stats, gs_stream_t stream);
+int gs_mcl_resample(const unsigned long long* cum, const int* particles, int n, unsigned long long W, unsigned long long q,
+                    int* out, gs_stream_t stream);
+
 /* ---- frame preprocessing of the dataset readers (src/datasets.py:96-143, 565-605), csrc/frame_prep.hip ----
  *
  * Semantics: tests/frame_prep_restatement.py, bit for bit (cv2.remap / cv2.resize INTER_LINEAR on 8-bit data,
